@@ -14,7 +14,14 @@ scaling, `value` = views processed by all ranks per second).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  `value` is the FUSED path (every edit of INTEGRATION.md section 4/4b applied:
-`config.path = "fused"`); at N=1 two more paths are timed for the record (`config.paths`): "zero_diff" = the reference's
+`config.path = "fused"`).  A plain run sets up, warms up, times the K steps, writes the last step's outputs when asked
+(`--dump-outputs DIR`) and prints the line: the headline and the statistics of its own timed loop, nothing else.  Everything
+below -- the sustained loop, the other MLP arithmetic, the rasterizer-heavy leg, the roofline leg and its counters, render
+ms/frame, the other call paths, the recorded PSNR parity, the CPU baseline and the `comm` block of N > 1 -- runs with `--full`:
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+With `--full`, at N=1 two more paths are timed for the record (`config.paths`): "zero_diff" = the reference's
 own files on the drop-in packages with no edit (our rasterizer called twice + geometry cache, everything else plain
 PyTorch: 24 grid_samples, nn.Linear stack, torch glue, conv2d SSIM, torch.optim.Adam) and "import_swap" = INTEGRATION
 section 4's one-line import swap only (fused HexPlane + MLP, the rest as zero_diff).
@@ -564,6 +571,92 @@ def workload_label(a, world=None):
     return f"synthetic street scene, NOT a BASELINE config (scale_mult {a.scale_mult})"
 
 
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: everything written, in all
+DUMP_ROWS = 16_384              # per-Gaussian arrays: this many rows, the same seeded sample for every array
+DUMP_DEFORMATION_ELEMS = 262_144
+
+
+def dump_outputs(out_dir, loss, pkg, pc):
+    """--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy, so that two builds run with the same arguments can
+    be compared array for array.  training_step's caller receives the loss and render()'s result dict (images, radii, visibility,
+    the deformation heads' dx / dshs, the regularisers); the step leaves the Gaussians' parameters, the deformation network and the
+    densification statistics updated in place (`param_*`, `deformation_params`, `stat_*`).  Images are written whole; per-Gaussian
+    arrays as one sample of DUMP_ROWS rows, seeded and drawn from the Gaussian count alone; the deformation network's parameters as
+    a seeded sample of their concatenation.  Should the total exceed DUMP_LIMIT_BYTES (images larger than the default workload's),
+    every image becomes a seeded sample of its elements.  float32 throughout (the integer and boolean results are exact in it), the
+    loss float64.  `viewspace_points` is left out: its values are uninitialised, only its gradient carries meaning, and the fused
+    step accumulates that into stat_xyz_gradient_accum directly.  -> sorted list of the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    dev = pc._xyz.device
+    P = int(pc._xyz.shape[0])
+    rng = np.random.default_rng(1234)
+    rows = torch.from_numpy(np.sort(rng.choice(P, size=min(P, DUMP_ROWS), replace=False))).to(dev)
+    f32 = lambda t: t.detach().float().cpu().numpy()
+    arrays = {"loss": np.asarray(float(loss), dtype=np.float64)}
+    for k in ("radii", "visibility_filter", "dx", "dshs"):
+        if pkg.get(k) is not None:
+            arrays[k] = f32(pkg[k].index_select(0, rows))
+    for k in ("dshs_l1", "plane_reg"):
+        if pkg.get(k) is not None:
+            arrays[k] = f32(pkg[k])
+    for k in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation"):
+        arrays["param" + k] = f32(getattr(pc, k).index_select(0, rows))
+    for k in ("xyz_gradient_accum", "denom", "max_radii2D"):
+        arrays["stat_" + k] = f32(getattr(pc, k).index_select(0, rows))
+    flat = torch.cat([p.detach().reshape(-1).float() for p in pc._deformation.parameters()])
+    pick = np.sort(rng.choice(flat.numel(), size=min(flat.numel(), DUMP_DEFORMATION_ELEMS), replace=False))
+    arrays["deformation_params"] = f32(flat[torch.from_numpy(pick).to(dev)])
+    images = {k: f32(pkg[k]) for k in ("render", "depth", "feat") if pkg.get(k) is not None}
+    rest = sum(v.nbytes for v in arrays.values())
+    if rest + sum(v.nbytes for v in images.values()) > DUMP_LIMIT_BYTES:
+        per = max(1, (DUMP_LIMIT_BYTES - rest) // (4 * len(images)))
+        for k, v in images.items():
+            images[k] = v.reshape(-1)[np.sort(rng.choice(v.size, size=min(v.size, per), replace=False))]
+    arrays.update(images)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return sorted(arrays)
+
+
+def headline_line(a, world, dt, t_enq, per_step, astat, V, R_mean, mlp_default):
+    """The result line as far as the headline goes: the K timed steps and what their own loop observed.  A plain run prints this;
+    --full adds the other legs to it."""
+    srt = sorted(per_step)
+    return {
+        "metric": "train_iters_per_sec", "value": round(world * a.steps / dt, 3), "unit": "iters/s", "n_gpus": world,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1000.0 * dt / a.steps, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        # one hipEvent pair per step on the launch stream (rank 0): stream time between step boundaries; next to the host's
+        # own time to ENQUEUE a step -- the step is GPU-bound while the second stays below the first
+        "step_ms_min": round(srt[0], 3), "step_ms_median": round(srt[len(srt) // 2], 3), "step_ms_max": round(srt[-1], 3),
+        "gpu_ms_per_step": round(sum(per_step) / len(per_step), 3),
+        "host_enqueue_ms_per_step": round(1000.0 * t_enq / a.steps, 3),
+        "gc_gen2_passes_in_timed_loop": GC_PASSES[0] if GC_PASSES else None,
+        "gc_gen1_passes_in_timed_loop": GC1_PASSES[0] if GC1_PASSES else None,
+        "longest_host_enqueue_of_one_step_ms": HOST_STALLS[0] if HOST_STALLS else None,
+        "gc_policy": "gc.collect() + gc.freeze() after the warm-up and gc.collect() before each timed loop; the collector stays enabled "
+                     "inside the loops (tools/soak.py times 600 steps with no such care: profiles/r04_soak.jsonl)",
+        "config": {"workload": workload_label(a, world) + f": {a.P} Gaussians, {a.height}x{a.width}, 3 cams x {a.frames} frames, fine stage "
+                               "(hexplane+deformation ON), RGB+depth render + feature render, L1+DSSIM+depthL2+featL2+regs, Adam",
+                   "path": "fused", "gaussians": a.P, "image": [a.height, a.width], "views_per_step_per_rank": 1,
+                   "scale_mult": a.scale_mult, "gaussians_in_morton_order": bool(a.reorder),
+                   "instances_R_per_view": round(R_mean) if R_mean is not None else None, "visible_V_per_view": round(V),
+                   "mean_tile_list_length": (round(R_mean / (((a.width + 15) // 16) * ((a.height + 15) // 16)), 1)
+                                             if R_mean is not None else None),
+                   "densify_bookkeeping_in_step": True,
+                   "rasterizer_forward": ("host-asynchronous, policy 'speculative' (arena sized for a speculative capacity, overflows checked after "
+                                          "each timed loop: s3g_raster_forward_async; the drop-in default 'verified' reads every forward's verdict)" if astat.get("enabled")
+                                          else "synchronous (one host wait per forward, like the reference)"),
+                   "raster_async": {k: astat.get(k) for k in ("enabled", "policy", "calls", "drained", "overflows", "overflows_in_discarded_first_attempt")
+                                    if k in astat},
+                   "parallelism": f"view-parallel dp{world}" if world > 1 else "single GPU",
+                   "mlp_arithmetic": (mlp_default + (": per-point GEMM chains on the bf16 matrix pipe, every fp32 operand split exactly into three "
+                                      "bf16 pieces, fp32 accumulation -- fp32 results (DESIGN 4.3); weight-gradient GEMMs exact fp32 MFMA"
+                                      if mlp_default == "bf16x3" else ": exact fp32 fma chains (v_mfma_f32_32x32x2_f32)"))},
+    }
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -595,6 +688,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-heavy-raster", action="store_true", help="skip the rasterizer-heavy leg (config.paths.heavy_raster)")
     ap.add_argument("--heavy-scale-mult", type=float, default=3.5)
     ap.add_argument("--heavy-steps", type=int, default=60)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else this script measures (sustained loop, other MLP arithmetic, "
+                         "rasterizer-heavy leg, roofline leg and counters, render ms/frame, config.paths, CPU baseline, comm block); "
+                         "the --no-* / --sustain-steps / --heavy-* options apply to these legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32, the loss "
+                         "float64; at most 64 MB in all: see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -781,10 +881,13 @@ def main(argv=None):
     raster_C.async_reset_statistics(device)
     comm.update(elems=0, events=[], sparse_rows=0)
     vis_masks, losses = [], []     # read after the timed region (workload statistics are not part of the step)
+    last = {}                      # the last timed step's (loss, render() result): --dump-outputs
 
     def keep(out):
         losses.append(out[0])
         vis_masks.append(out[1]["visibility_filter"])
+        if len(losses) == a.steps:
+            last["out"] = out
 
     headline_idx = list(range(a.warmup, a.warmup + a.steps))
     dt, t_enq, per_step = timed_loop(step, headline_idx, world, device, after_step=keep)
@@ -821,6 +924,19 @@ def main(argv=None):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt, t_enq = float(t[0].item()), float(t[1].item())
     comm_timed = {"elems": comm["elems"], "events": list(comm["events"]), "sparse_rows": comm["sparse_rows"]}
+    from s3gaussian_amd import mlp as _mlp
+    mlp_default = _mlp.get_mlp_arithmetic()
+    if a.dump_outputs and rank == 0:     # before anything else moves the parameters
+        dump_outputs(a.dump_outputs, *last["out"], pc)
+    if not a.full:
+        if rank == 0:
+            V = float(sum(int(m.sum()) for m in vis_masks)) / max(a.steps, 1)
+            R_mean = astat["mean_instances"] if (astat.get("drained") and astat.get("mean_instances")) else None
+            print(json.dumps(headline_line(a, world, dt, t_enq, per_step, astat, V, R_mean, mlp_default)))
+        if dist_on:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
 
     # ---- 1b. sustained throughput: a.sustain_steps more steps (default 300, ~2.3 s) over the same views, the interpreter's collector
     #          running as it pleases (no collect before, nothing frozen anew), walk-order re-sorts included -- the 20-step headline is a
@@ -849,8 +965,6 @@ def main(argv=None):
     #          rounds 3-5 had it the other way round.  (Every loop after the first ~2 s of load runs ~0.2 ms/step slower than the opening
     #          20-step burst on these boxes: read the pair against each other, not against the headline.)
     mlp_ab = None
-    from s3gaussian_amd import mlp as _mlp
-    mlp_default = _mlp.get_mlp_arithmetic()
     mlp_other = "f32" if mlp_default != "f32" else "bf16x3"
     if world == 1 and not dist_on and not a.no_alt_paths:
         try:
@@ -1210,50 +1324,20 @@ def main(argv=None):
                                                               "(re-sorted every 16th backward: a re-sort costs ~0.9 ms); scatter_ms_on_fresh_walk_orders "
                                                               "is the same kernel over 8 more steps with the orders re-sorted on every backward"}
         fwd = next((k for k in kernels if k["kernel"] == "s3g::blend_forward_kernel"), None)
-        srt = sorted(per_step)
-        out = {
-            "metric": "train_iters_per_sec", "value": round(world * a.steps / dt, 3), "unit": "iters/s", "n_gpus": world,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1000.0 * dt / a.steps, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            # one hipEvent pair per step on the launch stream (rank 0): stream time between step boundaries; next to the host's
-            # own time to ENQUEUE a step -- the step is GPU-bound while the second stays below the first
-            "step_ms_min": round(srt[0], 3), "step_ms_median": round(srt[len(srt) // 2], 3), "step_ms_max": round(srt[-1], 3),
-            "gpu_ms_per_step": round(sum(per_step) / len(per_step), 3),
-            "host_enqueue_ms_per_step": round(1000.0 * t_enq / a.steps, 3),
-            "instrumented_loop_ms_per_step": round(sum(per_step_instrumented) / len(per_step_instrumented), 3),
-            "gc_gen2_passes_in_timed_loop": GC_PASSES[0] if GC_PASSES else None,
-            "gc_gen1_passes_in_timed_loop": GC1_PASSES[0] if GC1_PASSES else None,
-            "longest_host_enqueue_of_one_step_ms": HOST_STALLS[0] if HOST_STALLS else None,
-            "sustained_iters_per_s": sustained["iters_per_s"] if sustained else None,
-            "step_ms_p99": sustained["step_ms_p99"] if sustained else None,
-            "sustained": sustained,
-            "gc_policy": "gc.collect() + gc.freeze() after the warm-up and gc.collect() before each timed loop; the collector stays enabled "
-                         "inside the loops (tools/soak.py times 600 steps with no such care: profiles/r04_soak.jsonl)",
-            "config": {"workload": workload_label(a, world) + f": {a.P} Gaussians, {a.height}x{a.width}, 3 cams x {a.frames} frames, fine stage "
-                                   "(hexplane+deformation ON), RGB+depth render + feature render, L1+DSSIM+depthL2+featL2+regs, Adam",
-                       "path": "fused", "gaussians": a.P, "image": [a.height, a.width], "views_per_step_per_rank": 1,
-                       "scale_mult": a.scale_mult, "gaussians_in_morton_order": bool(a.reorder), "instances_R_per_view": round(R_mean), "visible_V_per_view": round(V),
-                       "mean_tile_list_length": round(R_mean / (((a.width + 15) // 16) * ((a.height + 15) // 16)), 1),
-                       "densify_bookkeeping_in_step": True,
-                       "rasterizer_forward": ("host-asynchronous, policy 'speculative' (arena sized for a speculative capacity, overflows checked after "
-                                              "each timed loop: s3g_raster_forward_async; the drop-in default 'verified' reads every forward's verdict)" if astat.get("enabled")
-                                              else "synchronous (one host wait per forward, like the reference)"),
-                       "raster_async": {k: astat.get(k) for k in ("enabled", "policy", "calls", "drained", "overflows", "overflows_in_discarded_first_attempt")
-                                        if k in astat},
-                       "parallelism": f"view-parallel dp{world}" if world > 1 else "single GPU",
-                       "blend_forward_avg_ms": fwd["avg_launch_ms"] if fwd else None,
-                       "render_ms_per_frame": round(render_ms, 3), "render_ms_per_frame_median": round(render_median_ms, 3),
-                       "render_deform_infer_kernel_ms": round(infer_kernel_ms, 4) if infer_kernel_ms else None,
-                       "render_by_timestamp": render_by_timestamp,
-                       "render_arithmetic": _arith,
-                       f"render_ms_per_frame_{infer_other}": round(render_other_ms, 3),
-                       f"render_ms_per_frame_{infer_other}_median": round(render_other_median_ms, 3),
-                       "mlp_arithmetic": (mlp_default + (": per-point GEMM chains on the bf16 matrix pipe, every fp32 operand split exactly into three "
-                                          "bf16 pieces, fp32 accumulation -- fp32 results (DESIGN 4.3); weight-gradient GEMMs exact fp32 MFMA"
-                                          if mlp_default == "bf16x3" else ": exact fp32 fma chains (v_mfma_f32_32x32x2_f32)")),
-                       "render_loop_outliers": render_outliers},
-            "roofline": roof,
-        }
+        out = headline_line(a, world, dt, t_enq, per_step, astat, V, R_mean, mlp_default)
+        out.update({"instrumented_loop_ms_per_step": round(sum(per_step_instrumented) / len(per_step_instrumented), 3),
+                    "sustained_iters_per_s": sustained["iters_per_s"] if sustained else None,
+                    "step_ms_p99": sustained["step_ms_p99"] if sustained else None,
+                    "sustained": sustained})
+        out["config"].update({"blend_forward_avg_ms": fwd["avg_launch_ms"] if fwd else None,
+                              "render_ms_per_frame": round(render_ms, 3), "render_ms_per_frame_median": round(render_median_ms, 3),
+                              "render_deform_infer_kernel_ms": round(infer_kernel_ms, 4) if infer_kernel_ms else None,
+                              "render_by_timestamp": render_by_timestamp,
+                              "render_arithmetic": _arith,
+                              f"render_ms_per_frame_{infer_other}": round(render_other_ms, 3),
+                              f"render_ms_per_frame_{infer_other}_median": round(render_other_median_ms, 3),
+                              "render_loop_outliers": render_outliers})
+        out["roofline"] = roof
         if dist_on:
             # what the all-reduce cost this rank: stream time from "backward queued" to "optimizer step queued" minus the Adam
             # kernel itself = waiting for collectives + the small statistics reduces.  NO multi-GPU run has been measured in the

@@ -157,7 +157,7 @@ def test_the_drivers_own_bench_records_validate():
             continue
         if "roofline" not in parsed or "cpu_baseline" not in parsed or "path" not in parsed.get("config", {}):
             continue                                                      # round 1's line predates the contract's additions
-        validate_bench_line(parsed, default_workload=True)
+        validate_bench_line(parsed, default_workload=True, trimmed=True)
         seen += 1
     if not seen:
         pytest.skip("no driver record with a roofline object in the tree")

@@ -160,7 +160,7 @@ def test_one_rank_rccl_group_runs_the_data_parallel_step(gpu_device):
 
 def test_bench_under_the_forced_group_prints_a_comm_block_from_executed_collectives(gpu_device):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--P", "60000", "--width", "480",
-           "--height", "320", "--frames", "4", "--sustain-steps", "0"]
+           "--height", "320", "--frames", "4", "--sustain-steps", "0", "--full"]
     r = subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-6000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

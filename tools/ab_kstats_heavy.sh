@@ -6,7 +6,7 @@ for v in $1; do
   for mult in 3.5 1.0; do
     d=gpurun_out/kstats_${v}_$mult
     rm -rf $d
-    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python bench.py --steps 24 --warmup 4 --scale-mult $mult --no-cpu-baseline --no-alt-paths --no-pmc --no-heavy-raster --sustain-steps 0 > $d.log 2>&1
+    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python bench.py --full --steps 24 --warmup 4 --scale-mult $mult --no-cpu-baseline --no-alt-paths --no-pmc --no-heavy-raster --sustain-steps 0 > $d.log 2>&1
     echo "== $v, scale x $mult: $(grep '^{"metric' $d.log | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'it/s', d['ms_per_step'], 'ms (under the tracer)')")"
     python tools/kstats.py $d 40 | grep -E "${2:-sort_tiles}"
     rm -rf $d $d.log

@@ -2,8 +2,8 @@
 profiles/rNN_bench_pmc_fetch_write.csv and profiles/kernel_traffic.json (HBM bytes per launch of every s3g kernel).
 
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/pmc_f -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/pmc_w -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d pmc_f -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d pmc_w -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
   python tools/pmc_traffic.py /tmp/pmc_f /tmp/pmc_w <outdir>
 
 gfx950 correction (same guide): FETCH_SIZE counts 64 B per 128-B request -> doubled.  Both counters are in KB."""

@@ -1,5 +1,5 @@
 """Kernel sequence of ONE training iteration from a rocprofv3 kernel trace:  python tools/step_trace.py <rocprof out dir>
-(rocprofv3 --kernel-trace --output-format csv -d DIR -- python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-alt-paths)
+(rocprofv3 --kernel-trace --output-format csv -d DIR -- python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-alt-paths)
 Prints every dispatch between the last two adam_kernel launches: start offset, duration, gap to the previous kernel.
 `python tools/step_trace.py DIR render`: the same for one inference FRAME of tools/render_trace.py -- between the last two
 deform_infer_kernel launches."""

@@ -1,5 +1,5 @@
 """One training iteration of a rocprofv3 kernel trace with the QUEUE of every dispatch:  python tools/stream_trace.py <rocprof out dir>
-(rocprofv3 --kernel-trace --output-format csv -d DIR -- python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-alt-paths --sustain-steps 0)
+(rocprofv3 --kernel-trace --output-format csv -d DIR -- python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-alt-paths --sustain-steps 0)
 The iteration = everything between two consecutive mlp_forward_kernel launches of the HEADLINE loop (the K-th and (K+1)-th from the
 start of the trace, counting only intervals that contain a backward; default K = 4: past the warm-up, before the instrumented loop).  For every dispatch: start, duration, queue, and how much of it
 ran while a kernel of ANOTHER queue was running (optim.OverlappedStep: Adam of the per-Gaussian groups beside mlp_backward, the weight
