@@ -231,6 +231,11 @@ int s3g_raster_backward2_accum(const s3g_raster_inputs* in, const float* colors2
 void s3g_raster_set_exact_cull(int on);
 int s3g_raster_get_exact_cull(void);
 
+/* The blend backward skips, per wave of 64 pixels, the list entries behind the deepest contributor of the wave's own pixels
+ * (ON by default); every output is unchanged bit for bit.  Testing hook: 0 walks every wave from the deepest contributor of
+ * the whole tile.  Returns the previous setting.  Process-wide; applies to backwards issued after the call. */
+int s3g_raster_set_backward_wave_bounds(int on);
+
 /* Tile grids of more than 38 000 tiles (beyond 4K images) do not fit the binning pass's LDS histogram and are binned in
  * bands of consecutive tiles, one pair of launches per band; results are identical.  Testing hook: force a smaller band
  * (returns the previous size; tiles <= 0 restores the default) so the band path can be exercised on small images. */

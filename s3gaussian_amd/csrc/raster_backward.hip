@@ -14,8 +14,8 @@
 //      skipped outright when no lane of the wave is touched by the Gaussian;
 //   3. the 16 lane-rows of the tile (4 waves x 4 rows) park their sums in LDS slots, added in fixed order (no float atomics
 //      anywhere);
-//   4. once per 32-Gaussian batch each lane owns one Gaussian and stores its 10 sums as one 40-byte record at the
-//      instance's position in the sorted list (coalesced: consecutive lanes -> consecutive records);
+//   4. once per 32-Gaussian batch eight threads per Gaussian (one per float pair) add its 16 slots and store its 10 sums as
+//      one 40-byte record at the instance's position in the sorted list (consecutive lanes -> consecutive records);
 //   5. geometry_backward_kernel gathers each Gaussian's records through slot_pos[] (the instance -> position map
 //      the forward's sort emitted), applies the factored-out coefficients and runs the per-Gaussian chain.
 #include "geom_math.hpp"
@@ -109,18 +109,24 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint2* __restrict__
                       const float* __restrict__ depths, const float* __restrict__ final_Ts,
                       const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpixels,
                       const float* __restrict__ dL_dpixel_depths, float* __restrict__ records /*[R][NR]*/,
-                      const float* __restrict__ colors2, const float* __restrict__ dL_dpixels2) {
-  constexpr uint32_t BATCH = 32;  // Gaussians staged per round
+                      const float* __restrict__ colors2, const float* __restrict__ dL_dpixels2, int wave_bounds) {
+  constexpr uint32_t BATCH = 32;  // Gaussians staged per round (one bit each in a wave's visit mask)
   constexpr int NR = NX ? NREC + 4 : NREC;
   constexpr int SLOTS = 16;       // 4 waves x 4 rows of 16 lanes
   __shared__ StagedGaussian sg[BATCH];
   __shared__ float4 sg2[NX ? BATCH : 1];  // second image's colour
-  // one slot per (wave, row): combined in fixed order -> bit-reproducible sums.  Slots are padded by 16 floats: the four row
-  // leaders of a wave store the same [value][Gaussian] element of their four slots at once, and NR * BATCH floats is a
-  // multiple of the 64 banks (a 4-way conflict on each of the 13 stores: SQ_LDS_BANK_CONFLICT 1.8 cycles per LDS instruction)
+  // one slot per (wave, row): combined in fixed order -> bit-reproducible sums.  A slot holds NV value rows of RS floats (rows >= NV,
+  // which the transpose-reduce also produces, are not stored): 29.5 KiB of LDS in all for NX = 3, five workgroups per CU (16 rows
+  // of 32 + 16 floats: 35 KiB, four).  RS = BATCH + 1: the eight row leaders of a 32-lane group (four lane banks b x two slots)
+  // store row 4b + i of their slots at once; with 33-float rows the four b land 4 LDS banks apart and the two slots 13 (NX = 3)
+  // or 10 (NX = 0) apart: eight distinct banks (32-float rows: four leaders per bank).
   constexpr int NV = NX ? NREC + 3 : NREC;   // sums per visit
-  constexpr int SLOT_FLOATS = 16 * BATCH + 16;   // 16 value rows: the transpose-reduce stores four rows per bank, unconditionally
+  constexpr int RS = BATCH + 1;
+  constexpr int SLOT_FLOATS = NV * RS;
   __shared__ float acc[SLOTS][SLOT_FLOATS];
+  // bit j of visited[w]: wave w stored its four slots of entry j in this batch.  The slots are never cleared; the epilogue adds
+  // +0 for an entry a wave did not visit, which is what the cleared slot held -- the same additions in the same order.
+  __shared__ uint32_t visited[4];
 
   const uint32_t tile = xcd_swizzle(blockIdx.x, gridDim.x);
   if (tile >= (uint32_t)tiles) return;
@@ -136,6 +142,12 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint2* __restrict__
 
   const float T_final = inside ? final_Ts[pix] : 0.f;
   const uint32_t last_contributor = inside ? n_contrib[pix] : 0u;
+  // The wave's own bound: no pixel of the wave takes gradient from an entry at pos >= whi (the forward's per-wave maximum of
+  // n_contrib, whose tile maximum is tile_hi).  Entries between whi and hi are skipped by a scalar loop bound, before their LDS
+  // reads; they change no state and store no slot.  wave_bounds = 0 walks every wave from hi (the schedule before the bound).
+  uint32_t whi = last_contributor;
+  for (int off = 32; off >= 1; off >>= 1) whi = max(whi, (uint32_t)__shfl_xor((int)whi, off));
+  whi = wave_bounds ? __builtin_amdgcn_readfirstlane(whi) : hi;
   float gr = 0.f, gg = 0.f, gb = 0.f, gd = 0.f;
   if (inside) {
     gr = dL_dpixels[pix];
@@ -159,8 +171,7 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint2* __restrict__
 
   for (uint32_t done_cnt = 0; done_cnt < hi; done_cnt += BATCH) {
     const uint32_t cnt = min(BATCH, hi - done_cnt);
-    __syncthreads();  // previous batch fully consumed (sg, acc)
-    for (uint32_t e = tid; e < SLOTS * SLOT_FLOATS; e += 256) (&acc[0][0])[e] = 0.f;
+    __syncthreads();  // previous batch fully consumed (sg, acc, visited)
     if ((uint32_t)tid < cnt) {
       const uint32_t pos = hi - 1 - (done_cnt + tid);  // back to front
       const uint32_t id = point_list[rg.x + pos];
@@ -175,7 +186,10 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint2* __restrict__
     }
     __syncthreads();
 
-    for (uint32_t j = 0; j < cnt; j++) {
+    // entries j < j0 lie at pos >= whi (wave-uniform); a wave with j0 >= cnt goes straight to the barrier
+    const uint32_t j0 = hi - done_cnt > whi ? hi - done_cnt - whi : 0u;
+    uint32_t vis = 0u;
+    for (uint32_t j = j0; j < cnt; j++) {
       const uint32_t pos = hi - 1 - (done_cnt + j);  // 0-based position in the tile list
       // the reference's `contributor` equals pos after its decrement; it skips when contributor >= last_contributor
       bool valid = pos < last_contributor;
@@ -187,6 +201,7 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint2* __restrict__
       const float alpha = fminf(0.99f, B.y * G);
       valid = valid && !(q > 0.f) && !(alpha < 1.0f / 255.0f);
       if (__ballot(valid) == 0ull) continue;  // wave-uniform: this Gaussian misses all 64 pixels of the wave
+      vis |= 1u << j;
 
       float p_r = 0.f, p_g = 0.f, p_b = 0.f, p_d = 0.f, s0 = 0.f, sx = 0.f, sy = 0.f, sxx = 0.f, sxy = 0.f, syy = 0.f;
       float p2_r = 0.f, p2_g = 0.f, p2_b = 0.f;
@@ -224,26 +239,34 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint2* __restrict__
       const float vals[13] = {p_r, p_g, p_b, p_d, s0, sx, sy, sxx, sxy, syy, p2_r, p2_g, p2_b};
       float q4[4];
       row_transpose_reduce<NV>(vals, q4);
-      if ((lane & 3) == 0) {   // the first lane of bank b stores the row totals of values 4b .. 4b+3 (rows >= NV: never read)
-        float* aw = &acc[wave * 4 + (lane >> 4)][(lane & 12) * BATCH + j];
-        aw[0 * BATCH] = q4[0]; aw[1 * BATCH] = q4[1]; aw[2 * BATCH] = q4[2]; aw[3 * BATCH] = q4[3];
+      if ((lane & 3) == 0) {   // the first lane of bank b stores the row totals of values 4b .. 4b+3 (rows >= NV: not stored)
+        float* aw = &acc[wave * 4 + (lane >> 4)][(lane & 12) * RS + j];
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if ((lane & 12) + i < NV) aw[i * RS] = q4[i];
       }
     }
+    if (lane == 0) visited[wave] = vis;
     __syncthreads();
-    // Epilogue of the batch: lane t owns Gaussian t of the batch and stores its record (zeros if untouched).
-    if ((uint32_t)tid < cnt) {
-      const uint32_t pos = hi - 1 - (done_cnt + tid);
-      float2* rec = reinterpret_cast<float2*>(records + (size_t)(rg.x + pos) * NR);
+    // Epilogue of the batch: thread (k, g) adds values 2k, 2k+1 of Gaussian g over the 16 slots in fixed order (rows of wave 0,
+    // then wave 1, ...) and stores that float pair of its record (zeros if untouched).  Lanes 0-31 of a read are 32 consecutive
+    // floats: no bank conflicts.
+    const uint32_t g = (uint32_t)tid % BATCH, k = (uint32_t)tid / BATCH;
+    if (k < NR / 2 && g < cnt) {
+      uint32_t seen[4];   // all ones if the wave visited Gaussian g, else 0: slot value & seen = the slot or +0.0f
 #pragma unroll
-      for (int k = 0; k < NR / 2; k++) {
-        float lo = acc[0][2 * k * BATCH + tid], hi2 = acc[0][(2 * k + 1) * BATCH + tid];
+      for (int w = 0; w < 4; w++) seen[w] = 0u - ((visited[w] >> g) & 1u);
+      auto slot = [&](int q, uint32_t v) { return __uint_as_float(__float_as_uint(acc[q][v * RS + g]) & seen[q / 4]); };
+      const uint32_t v1 = 2 * k + 1 < (uint32_t)NV ? 2 * k + 1 : 2 * k;   // the pad float: any row of the slot, not used
+      float lo = slot(0, 2 * k), hi2 = slot(0, v1);
 #pragma unroll
-        for (int q = 1; q < SLOTS; q++) {  // fixed order: rows of wave 0, then wave 1, ...
-          lo += acc[q][2 * k * BATCH + tid];
-          hi2 += acc[q][(2 * k + 1) * BATCH + tid];
-        }
-        rec[k] = make_float2(lo, 2 * k + 1 < NV ? hi2 : 0.f);   // the pad float of a 14-float record stays 0
+      for (int q = 1; q < SLOTS; q++) {
+        lo += slot(q, 2 * k);
+        hi2 += slot(q, v1);
       }
+      const uint32_t pos = hi - 1 - (done_cnt + g);
+      float2* rec = reinterpret_cast<float2*>(records + (size_t)(rg.x + pos) * NR);
+      rec[k] = make_float2(lo, 2 * k + 1 < (uint32_t)NV ? hi2 : 0.f);   // the pad float of a 14-float record stays 0
     }
   }
 }
@@ -583,6 +606,13 @@ __global__ void __launch_bounds__(256) geometry_backward_kernel(const GeomBwdArg
 
 using namespace s3g;
 
+static bool g_wave_bounds = true;   // blend backward: per-wave visit bounds (s3g_raster_set_backward_wave_bounds)
+extern "C" int s3g_raster_set_backward_wave_bounds(int on) {
+  const int prev = g_wave_bounds ? 1 : 0;
+  g_wave_bounds = on != 0;
+  return prev;
+}
+
 extern "C" size_t s3g_raster_backward_workspace_bytes(int P, int R) {
   (void)P;
   return ((size_t)(R > 0 ? R : 0) * NREC * sizeof(float) + 127) & ~size_t(127);
@@ -629,7 +659,8 @@ static int raster_backward_impl(const char* who, const s3g_raster_inputs* in, co
     profile_begin(S3G_PROFILE_BLEND_BACKWARD, stream);
     hipLaunchKernelGGL(blend_backward_kernel<NX>, dim3(tile_blocks), dim3(256), 0, stream, W, H, gx, tiles, im.ranges,
                        im.tile_hi, b.point_list, in->background, g.means2D, g.conic_opacity, color_ptr, g.depths,
-                       im.final_T, im.n_contrib, dL_dpix, dL_dpix_depth, records, colors2, dL_dpix2);
+                       im.final_T, im.n_contrib, dL_dpix, dL_dpix_depth, records, colors2, dL_dpix2,
+                       g_wave_bounds ? 1 : 0);
     profile_end(S3G_PROFILE_BLEND_BACKWARD, stream, (double)R, (double)W * H);
     S3G_KERNEL_CHECK(stream, debug);
   }
