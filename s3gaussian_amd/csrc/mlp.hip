@@ -1924,7 +1924,6 @@ extern "C" int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const floa
   if (P == 0) return S3G_OK;
   if (int e = mlp_set_attrs()) return e;
   hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(mlp_pack_kernel, dim3(NSLAB + 1), dim3(256), 0, stream, *w, stash);
   MlpFwdArgs a;
   a.P = P; a.x = features; a.packed = stash; a.dx = dx; a.dshs = dshs; a.feat = feat;
   a.stash = save_activations ? stash + PACK_TOTAL : nullptr;
@@ -1932,9 +1931,13 @@ extern "C" int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const floa
   const int ntiles = (P + MT - 1) / MT;
   const int blocks = min((ntiles + NWAVE - 1) / NWAVE, 256);
   const int arith = g_mlp_arithmetic.load(std::memory_order_relaxed);
-  if (arith == S3G_MLP_BF16X3)   // the forward's pre-split image, behind the fp32 one (the backward packs its own: it may run in another mode)
+  // each arithmetic packs only the image its forward kernel reads: the pre-split one sits behind the slot of the fp32 one, which a
+  // bf16x3 forward leaves unwritten (a backward in another mode packs the fp32 image itself)
+  if (arith == S3G_MLP_BF16X3)
     hipLaunchKernelGGL(mlp_pack_presplit_fwd_kernel, dim3((tpw::WORDS + 255) / 256), dim3(256), 0, stream, *w,
                        reinterpret_cast<uint32_t*>(stash + PACK_FLOATS));
+  else
+    hipLaunchKernelGGL(mlp_pack_kernel, dim3(NSLAB + 1), dim3(256), 0, stream, *w, stash);
   profile_begin(S3G_PROFILE_MLP_FORWARD, stream);
   if (arith == S3G_MLP_BF16X3) {
     MlpFwdArgs s = a;
@@ -1989,10 +1992,13 @@ static int mlp_backward_impl(const s3g_mlp_params* w, int P, const float* featur
   const int ntiles = (P + MT - 1) / MT;
   const int blocks = min((ntiles + NWAVE - 1) / NWAVE, 256);
   const int arith = g_mlp_arithmetic.load(std::memory_order_relaxed);
-  // S3G_MLP_BF16X3: the transposed pre-split image goes into the slot the stash reserves for it (the caller's buffer: only this region is written)
+  // S3G_MLP_BF16X3: the transposed pre-split image goes into the slot the stash reserves for it; the other modes read the fp32 image,
+  // which a bf16x3 forward does not build, so they pack it into its slot (the caller's buffer: only the image regions are written)
   float* img = const_cast<float*>(stash_) + PACK_FLOATS + tpw::WORDS;
   if (arith == S3G_MLP_BF16X3)
     hipLaunchKernelGGL(mlp_pack_presplit_bwd_kernel, dim3((tbw::WORDS + 255) / 256), dim3(256), 0, stream, *w, reinterpret_cast<uint32_t*>(img));
+  else
+    hipLaunchKernelGGL(mlp_pack_kernel, dim3(NSLAB + 1), dim3(256), 0, stream, *w, const_cast<float*>(stash_));
   profile_begin(S3G_PROFILE_MLP_BACKWARD, stream);
   if (arith == S3G_MLP_BF16X3) {
     MlpBwdArgs sb = b;
