@@ -5,9 +5,11 @@
   training_loss()     <- train.py:395-425 loss assembly (L1 + dx/dshs reg + depth L2 + plane regulation + DSSIM + feat L2)
   training_step()     <- train.py:372-437,521-522 for one view (batch_size = 1)
 
-Everything outside that path (data readers, densification, checkpoints, evaluation, logging) stays with the
-reference and is NOT rebuilt here (DESIGN.md "out of scope").  The losses are plain PyTorch on the
-GPU exactly like the reference's utils/loss_utils.py; the operators underneath are the HIP library.
+Adaptive density control -- GaussianParams.densify / prune / reset_opacity and the schedule of train.py:494-516 -- lives in
+density.py on kernels of its own (include/s3g_density.h).  Everything else outside that path (data readers, checkpoints'
+surroundings, evaluation, logging) stays with the reference and is NOT rebuilt here (DESIGN.md "out of
+scope").  The losses are plain PyTorch on the GPU exactly like the reference's utils/loss_utils.py; the operators underneath are
+the HIP library.
 """
 from __future__ import annotations
 
@@ -57,6 +59,8 @@ def inverse_sigmoid(x):
 class GaussianParams(nn.Module):
     """Parameter store with the reference's attribute names (`_xyz`, `_features_dc`, ..., `_deformation`)."""
 
+    percent_dense = 0.01     # scene/gaussian_model.py:171 takes it from the optimization arguments; training_setup does too
+
     def __init__(self, sh_degree: int, hyper: SimpleNamespace):
         super().__init__()
         self.max_sh_degree = sh_degree
@@ -105,6 +109,7 @@ class GaussianParams(nn.Module):
     def training_setup(self, opt: SimpleNamespace):
         """Adam groups of scene/gaussian_model.py:177-189 (eps 1e-15)."""
         s = self.spatial_lr_scale
+        self.percent_dense = getattr(opt, "percent_dense", self.percent_dense)
         groups = [
             {"params": [self._xyz], "lr": opt.position_lr_init * s, "name": "xyz"},
             {"params": list(self._deformation.get_mlp_parameters()), "lr": opt.deformation_lr_init * s, "name": "deformation"},
@@ -126,6 +131,23 @@ class GaussianParams(nn.Module):
         else:
             self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
         return self.optimizer
+
+    # ---- adaptive density control (density.py; the reference's argument order, its unused trailing arguments accepted and ignored) ----
+    def densify(self, max_grad, min_opacity, extent, max_screen_size, density_threshold=None, displacement_scale=None,
+                model_path=None, iteration=None, stage=None, **kw):
+        """scene/gaussian_model.py:673-678.  kw: noise / seed / return_noise / percent_dense of density.densify."""
+        from . import density
+        return density.densify(self, max_grad, extent, **kw)
+
+    def prune(self, max_grad, min_opacity, extent, max_screen_size):
+        """scene/gaussian_model.py:661-670."""
+        from . import density
+        return density.prune(self, min_opacity, extent, max_screen_size)
+
+    def reset_opacity(self):
+        """scene/gaussian_model.py:350-353."""
+        from . import density
+        return density.reset_opacity(self)
 
     # ---- optional maintenance: keep the Gaussians in a spatially coherent order ------------------------------------------
     @torch.no_grad()
