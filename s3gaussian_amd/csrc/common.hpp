@@ -166,6 +166,13 @@ __device__ __forceinline__ float4 xform_4x4(const float3 p, const float* __restr
                      M[2] * p.x + M[6] * p.y + M[10] * p.z + M[14], M[3] * p.x + M[7] * p.y + M[11] * p.z + M[15]);
 }
 
+// The lanes of ONE wave hand data to each other through LDS: earlier LDS writes of the wave are visible to its later reads.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // XCD-aware tile order: hardware places workgroup b on XCD (b % 8); give each XCD a contiguous band of
 // tiles so neighbouring tiles (which share most of their Gaussians) hit the same 4 MiB L2.
 __device__ __forceinline__ uint32_t xcd_swizzle(uint32_t bid, uint32_t nblocks) {

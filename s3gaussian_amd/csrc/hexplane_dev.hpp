@@ -1,4 +1,4 @@
-// Device-side building blocks of the HexPlane sampler shared by hexplane.hip (forward / backward kernels) and mlp.hip (the fused
+// Device-side building blocks of the HexPlane sampler shared by hexplane.hip (forward / backward kernels) and deform_infer.hip (the fused
 // inference kernel HexPlane (+) deformation MLP): tap construction and sharing through LDS, channel-last texel loads, the
 // uniform-time row tables.  Private to libs3g.so (not part of the C ABI).
 #pragma once
@@ -174,11 +174,6 @@ __device__ __forceinline__ PointTap read_tap(const float4* __restrict__ taps, in
 }
 __device__ __forceinline__ float4 texel4(const float* __restrict__ plane, uint32_t byte_off) {
   return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(plane) + byte_off);
-}
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 __device__ constexpr bool IS_TIME_PLANE[6] = {false, false, true, false, true, true};
 

@@ -122,7 +122,7 @@ def test_split_bf16_inference_has_fp32_accuracy(gpu_device, P, tmode):
 @pytest.mark.parametrize("tmode,launches", [("uniform", 1000), ("per_point", 200)])
 def test_split_inference_is_bit_reproducible_1000_launches(gpu_device, tmode, launches):
     """The split kernel's staging store once read stale registers for the last quarter of a wave (packed-fp32 VALU result -> DS store
-    data while the other wave of the SIMD issues bf16 MFMAs; csrc/mlp.hip, profiles/r04_split_hazard_isa.txt): two wrong rows about
+    data while the other wave of the SIMD issues bf16 MFMAs; csrc/deform_infer.hip, profiles/r04_split_hazard_isa.txt): two wrong rows about
     once per thousand (level, round) steps, different rows every launch -- ~800 rows per launch at 1.2 M points, which four launches
     catch only sometimes at small P.  The stress form: 1000 launches at BASELINE size, each compared with the first ON THE DEVICE, bit
     for bit (profiles/r04_split_hazard.jsonl: the unprotected build fails this with 110 872 wrong rows; the tree: 0).  The same

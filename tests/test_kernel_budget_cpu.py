@@ -54,8 +54,9 @@ def test_hexplane_kernels_keep_their_occupancy(built):
 
 def test_mlp_and_raster_kernels_do_not_spill(built):
     mlp = _resources("mlp.o")
-    for needle in ("mlp_forward_kernelILb0E", "mlp_backward_kernelILb0E", "mlp_wgrad_all_kernel", "deform_infer_kernelILb1ELb0E"):
-        vgpr, scratch = _one(mlp, needle)
+    for obj, needle in ((mlp, "mlp_forward_kernelILb0E"), (mlp, "mlp_backward_kernelILb0E"), (_resources("mlp_wgrad.o"), "mlp_wgrad_all_kernel"),
+                        (_resources("deform_infer.o"), "deform_infer_kernelILb1ELb0E")):
+        vgpr, scratch = _one(obj, needle)
         assert vgpr <= 256 and scratch == 0, (needle, vgpr, scratch)
     # round 5: the bf16x3 chains with pre-split weight images (159 KiB of LDS: one workgroup per CU, two waves per SIMD)
     vgpr, scratch = _one(mlp, "mlp_backward_presplit_kernel")
@@ -136,11 +137,11 @@ def test_split_inference_kernel_keeps_the_guard_of_its_staging_stores(built):
     """VERDICT r4 weak #12.  deform_infer_kernel<UT, SPLIT = true> parks the sampler's float4 products in LDS beside the other wave's
     bf16 (XDL) MFMAs.  A DS store whose data registers were last written by a PACKED fp32 instruction reads stale data for the last
     quarter of the wave there (110 872 wrong rows in 1000 launches, profiles/r04_split_hazard.jsonl); the cure is a register
-    dependency on a single-pass write -- four `v_mov_b32 vN, vN` in front of the store (mlp.hip) -- which lives or dies with the
+    dependency on a single-pass write -- four `v_mov_b32 vN, vN` in front of the store (deform_infer.hip) -- which lives or dies with the
     compiler not folding the moves away.  This asserts it on the BUILT code object: in both split kernels every 16-byte staging store
     takes its data from v_mov_b32, none takes it from v_pk_mul_f32; the exact kernels (no XDL ops beside them) show what the
     unguarded form looks like."""
-    k = _disassemble("mlp.o")
+    k = _disassemble("deform_infer.o")
     def one(needle):
         hits = [v for n, v in k.items() if needle in n]
         assert len(hits) == 1, needle

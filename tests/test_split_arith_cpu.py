@@ -1,4 +1,4 @@
-"""The arithmetic behind S3G_MLP_BF16X3 / s3g_deform_infer_split (s3gaussian_amd/csrc/mlp.hip: split_pair, mfma_split), restated in
+"""The arithmetic behind S3G_MLP_BF16X3 / s3g_deform_infer_split (s3gaussian_amd/csrc/mlp_dev.hpp: split_pair, mfma_split), restated in
 numpy: every fp32 number is the EXACT sum of three round-to-nearest bf16 pieces, and the six piece products of weight >= 2^-16
 reproduce a product to <= 2^-23 relative.  Also pins split_feature(): the element order shared by the A fragments of the packed image
 and the accumulator registers that become the B operand.  (The kernels themselves are checked on the GPU: tests/test_mlp_gpu.py,
@@ -68,7 +68,7 @@ def test_dot_products_have_fp32_accuracy():
 
 
 def test_split_feature_is_the_accumulator_register_order():
-    """mlp.hip: register r of lane l holds feature rrow(r) + 4*(l >> 5) of point l & 31 (rrow(r) = (r & 3) + 8 * (r >> 2)); at K step
+    """mlp_dev.hpp: register r of lane l holds feature rrow(r) + 4*(l >> 5) of point l & 31 (rrow(r) = (r & 3) + 8 * (r >> 2)); at K step
     ks = 2*mbi + s the lane's eight B elements are registers 8s .. 8s+7 of block mbi: split_feature(ks, h, e) must name them."""
     rrow = lambda r: (r & 3) + 8 * (r >> 2)
     split_feature = lambda ks, h, e: 16 * ks + 4 * h + (e & 3) + 8 * (e >> 2)

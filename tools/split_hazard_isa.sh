@@ -1,15 +1,15 @@
 #!/bin/bash
-# profiles/r04_split_hazard_isa.txt: the staging store of deform_infer_kernel<true, true> (csrc/mlp.hip) and the instructions before
+# profiles/r04_split_hazard_isa.txt: the staging store of deform_infer_kernel<true, true> (csrc/deform_infer.hip) and the instructions before
 # it, for the tree and the two variant sources of tools/variants/r04_split_hazard.py (CPU only: hipcc cross-compiles, llvm-objdump).
 set -euo pipefail
 ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"; LL=/opt/rocm/lib/llvm/bin; T="$(mktemp -d)"; trap 'rm -rf "$T"' EXIT
 dump() { $LL/llvm-objcopy --dump-section .hip_fatbin=$T/fb "$1" && $LL/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$T/fb --output=$T/co --unbundle && $LL/llvm-objdump -d --no-show-raw-insn $T/co > "$2"; }
-dump "$ROOT/s3gaussian_amd/lib/mlp.o" $T/tree.s
+dump "$ROOT/s3gaussian_amd/lib/deform_infer.o" $T/tree.s
 python - "$ROOT" "$T" <<'PY'
 import os, runpy, subprocess, sys
 root, T = sys.argv[1], sys.argv[2]
 V = runpy.run_path(os.path.join(root, "tools/variants/r04_split_hazard.py"))["VARIANTS"]
-src = open(os.path.join(root, "s3gaussian_amd/csrc/mlp.hip")).read()
+src = open(os.path.join(root, "s3gaussian_amd/csrc/deform_infer.hip")).read()
 for name, (_, edits) in V.items():
     s = src
     for old, new in edits:
@@ -28,7 +28,7 @@ python - "$T" > "$ROOT/profiles/r04_split_hazard_isa.txt" <<'PY'
 import re, sys
 T = sys.argv[1]
 print("""# ISA of the split-arithmetic inference kernel deform_infer_kernel<true, true> around its staging store (VERDICT r3 Weak #6 / ADVICE r3).
-# llvm-objdump (hipcc 7.2, gfx950) of four builds of csrc/mlp.hip; measured behaviour of each in profiles/r04_split_hazard.jsonl
+# llvm-objdump (hipcc 7.2, gfx950) of four builds of csrc/deform_infer.hip; measured behaviour of each in profiles/r04_split_hazard.jsonl
 # (tools/diag_split.py: every launch compared bit for bit with the first, 1000 launches at 1.2 M points, 400 at 70 001):
 #   split_nopad  nothing between the products and the store           -> 110 872 wrong rows / 1000 launches (lanes 48..63 of a wave)
 #   split_nops   16 wait states (round 3)                             -> 0
