@@ -1,4 +1,5 @@
-// Device-side building blocks of the HexPlane sampler shared by hexplane.hip (forward / backward kernels) and deform_infer.hip (the fused
+// Device-side building blocks of the HexPlane sampler shared by the hexplane*.hip files (forward / backward kernels; what only the
+// backward's files share is in hexplane_bwd.hpp) and deform_infer.hip (the fused
 // inference kernel HexPlane (+) deformation MLP): tap construction and sharing through LDS, channel-last texel loads, the
 // uniform-time row tables.  Private to libs3g.so (not part of the C ABI).
 #pragma once
@@ -10,16 +11,10 @@ namespace s3g {
 
 constexpr int HEXC = S3G_HEX_CHANNELS;
 typedef float f4v __attribute__((ext_vector_type(4)));
-constexpr bool G_NONTEMPORAL = true;         // streaming stores of the gradient slab: point pass 1.83 -> 1.60 ms
-constexpr bool FEAT_NONTEMPORAL = true;      // forward's feature rows
-constexpr bool GFEAT_NONTEMPORAL = true;     // point pass: dL/dfeature rows (read once)
-constexpr bool G_NONTEMPORAL_LOAD = true;    // and streaming loads in the scatter: 1.28 -> 1.23 ms
 
 // Workgroups are dealt to the 8 XCDs round-robin (block b -> XCD b % 8) and every XCD has its own L2.  With the points in
 // spatial order, giving XCD k the k-th CONTIGUOUS eighth of the groups keeps each texel line in one L2 instead of eight.
-constexpr bool XCD_CONTIGUOUS = true;
 __device__ __forceinline__ int xcd_group(int b, int nb) {
-  if (!XCD_CONTIGUOUS) return b;
   const int per = nb >> 3;
   return b < (per << 3) ? (b & 7) * per + (b >> 3) : b;
 }
@@ -177,7 +172,6 @@ __device__ __forceinline__ float4 texel4(const float* __restrict__ plane, uint32
 }
 __device__ constexpr bool IS_TIME_PLANE[6] = {false, false, true, false, true, true};
 
-
 // ---- uniform time: the (axis, t) planes collapse to 1-D row tables ---------------------------------------------------
 // When every point carries the same t, the t half of the bilinear footprint is the same for all of them:
 //   R[x][c] = P[y0][x][c] * (y1 - iy) + P[y1][x][c] * (iy - y0)       (iy from time[0], exactly as make_tap computes it)
@@ -276,6 +270,5 @@ static inline int check_desc(const s3g_hexplane_desc* d) {
   }
   return S3G_OK;
 }
-
 
 }  // namespace s3g

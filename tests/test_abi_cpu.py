@@ -197,3 +197,42 @@ def test_removed_hexplane_algorithm_is_refused_not_remapped():
     L.s3g_hexplane_backward_algo.restype = C.c_int
     rc = L.s3g_hexplane_backward_algo(None, C.c_int(0), None, None, None, None, C.c_int(1), None, None, None, None, C.c_int(0), None)
     assert rc == 1 and b"removed in ABI 12" in L.s3g_last_error()
+
+
+def test_hexplane_workspace_layout_is_what_the_single_file_library_carved():
+    """The carve functions of csrc/hexplane.hip are host code: no kernel comparison covers them.  The sizes they report for the
+    reference field (pipeline.default_hyper: 4 levels, 64 x 64 x 64 x 25 times 1 / 2 / 4 / 8 on the spatial axes) are compared with
+    literals recorded from the library of commit 7273f3a, the last one with the whole sampler in one hexplane.hip.  P = 999 999 and
+    1 000 000 straddle the switch of segment_length (128 -> 256 sorted points per walker), which the deterministic records follow."""
+    import ctypes as C
+    from s3gaussian_amd import hexplane
+    from s3gaussian_amd.pipeline import default_hyper
+    L = hexplane._bind()
+    hyper = default_hyper()
+    base = hyper.kplanes_config["resolution"]
+    assert list(base) == [64, 64, 64, 25] and list(hyper.multires) == [1, 2, 4, 8]
+    assert L.s3g_hexplane_sort_state_words(4) == 25
+    PS = (0, 1, 999_999, 1_000_000)
+    # (deterministic, uniform_time) -> forward bytes, backward bytes per P       recorded from 7273f3a
+    recorded = {
+        (0, 0): (0, (6842496, 6843520, 670841984, 670842496)),
+        (0, 1): (368640, (7579776, 7580800, 671579264, 671579776)),
+        (1, 0): (0, (546542976, 546556288, 1283299712, 1246927744)),
+        (1, 1): (368640, (547280256, 547293568, 1284036992, 1247665024)),
+    }
+    prev = L.s3g_hexplane_get_deterministic()
+    try:
+        for (det, ut), (fwd, bwd) in recorded.items():
+            L.s3g_hexplane_set_deterministic(det)
+            d = hexplane._HexDesc()
+            d.levels = len(hyper.multires)
+            d.uniform_time = ut
+            for l, m in enumerate(hyper.multires):
+                for k in range(4):
+                    d.res[l][k] = base[k] * m if k < 3 else base[k]
+            assert L.s3g_hexplane_forward_workspace_bytes(C.byref(d)) == fwd, (det, ut)
+            for have_features in (0, 1):       # unused since ABI 12, still part of the signature
+                got = tuple(L.s3g_hexplane_backward_workspace_bytes(C.byref(d), P, have_features) for P in PS)
+                assert got == bwd, (det, ut, have_features, got)
+    finally:
+        L.s3g_hexplane_set_deterministic(prev)

@@ -1,9 +1,12 @@
-"""The walker's remembered footprint of hexplane.hip::foot1_add_t (hit path, evict, shift down / right), modelled statement by
+"""The walker's remembered footprint of hexplane_scatter.hip::foot1_add_t (hit path, evict, shift down / right), modelled statement by
 statement in Python: whatever sequence of bilinear taps a walker sees, the flushed sums plus the final flush must equal the
 direct scatter.  Integer-valued gradients and weights make every order of summation exact.  Test infrastructure only
 (documents why the miss path conserves every contribution; the compiled kernel is checked by tests/test_hexplane_gpu.py).
 (Rounds 1-4 carried a two-entry cache with an MRU bit, foot2_add; it went with the finest-level walk orders in round 5.  The model
-below takes the gradient already divided by the sample: the division is a per-call scalar and does not touch the bookkeeping.)"""
+below takes the gradient already divided by the sample: the division is a per-call scalar and does not touch the bookkeeping.
+Since hexplane.hip was split the miss path of foot1_add_t is the same statements without the always-true FOOT_SHIFT switch (the
+model never had one), the per-corner accumulation -- the `for k` loop of add() -- lives in foot1_accumulate, and foot1_flush_all /
+foot_flush are unchanged: the model still matches statement for statement.)"""
 import numpy as np
 import pytest
 

@@ -289,7 +289,7 @@ def test_product_rule_fallback_matches_the_default_backward(gpu_device, tmode, m
 
 def test_every_walk_order_is_sorted_by_its_own_levels_cells(gpu_device):
     """Round 4: the scatter walks every (orientation, level) in an order sorted by THAT level's (major, minor) texel cells
-    (csrc/hexplane.hip::sort_cell / order_key; sort_state layout in include/s3g_hexplane.h).  A wrong key would not change any result
+    (csrc/hexplane_bwd.hpp::sort_cell, csrc/hexplane_sort.hip::order_key; sort_state layout in include/s3g_hexplane.h).  A wrong key would not change any result
     -- the orders only steer the walks -- it would silently bring back the flush storm, so the orders themselves are checked: keys
     recomputed here in the kernel's fp32 arithmetic must be non-decreasing along every order, every order must be a permutation,
     and comp must be the composition with the processing order."""

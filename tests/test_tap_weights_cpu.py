@@ -1,4 +1,4 @@
-"""hexplane.hip shares a bilinear tap between lanes as (nw key, ix - x0, iy - y0) and recomputes x1 - ix as 1 - (ix - x0).
+"""hexplane_dev.hpp (produce_taps / read_tap) shares a bilinear tap between lanes as (nw key, ix - x0, iy - y0) and recomputes x1 - ix as 1 - (ix - x0).
 Claim in the source: bit-identical to torch's grid_sampler weights, because ix - x0 is exact in fp32 (Sterbenz; x0 = 0
 trivially) and both expressions are then the correct rounding of the same real number.  Checked here in numpy fp32 on the
 whole coordinate range the sampler produces (align_corners unnormalisation, border clip), incl. every representable value

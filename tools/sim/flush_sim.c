@@ -1,4 +1,4 @@
-// Counts the line-atomics the HexPlane scatter walk issues (csrc/hexplane.hip::foot2_add_t, statement by statement: two-entry
+// Counts the line-atomics the HexPlane scatter walk issues (foot2_add_t of rounds 1-4; today's one-entry form is csrc/hexplane_scatter.hip::foot1_add_t -- statement by statement: two-entry
 // footprint cache, no MRU swap, shift reuse on the miss path, everything flushed at the end of a segment) for a given walk order,
 // so that alternative orders can be priced on the CPU before a kernel is written.   gcc -O2 -o flush_sim flush_sim.c
 // stdin-free: flush_sim <keys.bin> <flags.bin> <n> <W> <row:0|1> <seg_len> <entries:1|2>
