@@ -4,12 +4,13 @@
   render()            <- gaussian_renderer/__init__.py:23-210 (same arguments, same result-dict keys)
   training_loss()     <- train.py:395-425 loss assembly (L1 + dx/dshs reg + depth L2 + plane regulation + DSSIM + feat L2)
   training_step()     <- train.py:372-437,521-522 for one view (batch_size = 1)
+  evaluate()          <- the metric part of utils/video_utils.py:169-241 (PSNR, SSIM and their masked forms per frame, metrics.py)
 
 Adaptive density control -- GaussianParams.densify / prune / reset_opacity and the schedule of train.py:494-516 -- lives in
 density.py on kernels of its own (include/s3g_density.h).  Everything else outside that path (data readers, checkpoints'
-surroundings, evaluation, logging) stays with the reference and is NOT rebuilt here (DESIGN.md "out of
-scope").  The losses are plain PyTorch on the GPU exactly like the reference's utils/loss_utils.py; the operators underneath are
-the HIP library.
+surroundings, LPIPS and the videos of the evaluation, logging) stays with the reference and is NOT rebuilt here (SURVEY.md
+section 2, DESIGN.md "out of scope").  The losses are plain PyTorch on the GPU exactly like the reference's utils/loss_utils.py;
+the operators underneath are the HIP library.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import metrics as _metrics
 from .deformation import deform_network
 from .glue import activations_and_colors
 from .knn import distCUDA2
@@ -593,6 +595,30 @@ def _plane_smoothness(t):
 def psnr(img1, img2):
     mse = ((img1 - img2) ** 2).reshape(img1.shape[0], -1).mean(1, keepdim=True)
     return 20 * torch.log10(1.0 / torch.sqrt(mse))
+
+
+def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: torch.Tensor, masks=None, stage="fine",
+             return_decomposition=False) -> Dict:
+    """The metric part of the reference's evaluation loop (utils/video_utils.py:169-241, 301-307): every camera is rendered under
+    no_grad, frame i's {psnr, ssim, masked_psnr, masked_ssim, masked_pixels} goes into row i of one [N,5] device tensor
+    (metrics.image_metrics), and that tensor is read back ONCE after the last frame.  masks: None, or one entry per camera (None
+    for a camera without a dynamic mask).  The four scalars are the reference's `non_zero_mean`: the mean over the frames that
+    contributed -- for the masked pair the frames with at least one masked pixel -- and -1 when none did.  "per_frame" is the
+    [N,5] table on the host.  LPIPS is not computed."""
+    n = len(cameras)
+    if len(gt_images) != n or (masks is not None and len(masks) != n):
+        raise RuntimeError("evaluate: one ground-truth image (and one mask entry) per camera")
+    table = torch.empty((n, _metrics.RECORD), dtype=torch.float64, device=pc.get_xyz.device)
+    with torch.no_grad():
+        for i, cam in enumerate(cameras):
+            pkg = render(cam, pc, pipe, bg, stage=stage, return_decomposition=return_decomposition)
+            _metrics.image_metrics(pkg["render"], gt_images[i], None if masks is None else masks[i], out=table[i])
+    per_frame = table.cpu()
+    non_zero_mean = lambda x: float(x.sum() / len(x)) if len(x) > 0 else -1      # video_utils.py:44-46
+    contributed = per_frame[:, _metrics.MASKED_PIXELS] > 0
+    return {"psnr": non_zero_mean(per_frame[:, _metrics.PSNR]), "ssim": non_zero_mean(per_frame[:, _metrics.SSIM]),
+            "masked_psnr": non_zero_mean(per_frame[contributed, _metrics.MASKED_PSNR]),
+            "masked_ssim": non_zero_mean(per_frame[contributed, _metrics.MASKED_SSIM]), "per_frame": per_frame}
 
 
 _weight_cache: Dict = {}
