@@ -186,6 +186,19 @@ class Deformation(nn.Module):
     def drop_inference_cache(self) -> None:
         self.__dict__.pop("_infer_cache", None)
 
+    def inference_cache_entry(self):
+        """The cached evaluation (or None), for a caller that evaluates one timestamp ahead of the one it renders
+        (pipeline.render_flows) and puts this one back with install_inference_cache before the render that should hit it."""
+        return self.__dict__.get("_infer_cache")
+
+    def install_inference_cache(self, entry) -> None:
+        """Makes an entry taken from inference_cache_entry() the cached evaluation again.  Its key still names the versions of
+        everything the outputs depend on: an entry that has gone stale in the meantime simply misses."""
+        if entry is not None:
+            from . import raster_C
+            self.__dict__["_infer_cache"] = entry
+            raster_C._infer_cache_owners.add(self)
+
     def forward_dynamic(self, rays_pts_emb, scales_emb, rotations_emb, opacity_emb, shs_emb, time_feature, time_emb):
         a = self.args
         if self._fused_ok() and rays_pts_emb.is_cuda:

@@ -5,10 +5,11 @@
   training_loss()     <- train.py:395-425 loss assembly (L1 + dx/dshs reg + depth L2 + plane regulation + DSSIM + feat L2)
   training_step()     <- train.py:372-437,521-522 for one view (batch_size = 1)
   evaluate()          <- the metric part of utils/video_utils.py:169-241 (PSNR, SSIM and their masked forms per frame, metrics.py)
+  render_flows()      <- the flow part of utils/video_utils.py:203-209, 252-299 (forward / backward scene-flow images, flow.py)
 
 Adaptive density control -- GaussianParams.densify / prune / reset_opacity and the schedule of train.py:494-516 -- lives in
 density.py on kernels of its own (include/s3g_density.h).  Everything else outside that path (data readers, checkpoints'
-surroundings, LPIPS and the videos of the evaluation, logging) stays with the reference and is NOT rebuilt here (SURVEY.md
+surroundings, LPIPS and the video files of the evaluation, logging) stays with the reference and is NOT rebuilt here (SURVEY.md
 section 2, DESIGN.md "out of scope").  The losses are plain PyTorch on the GPU exactly like the reference's utils/loss_utils.py;
 the operators underneath are the HIP library.
 """
@@ -407,13 +408,19 @@ class _LazyResult(dict):
 
 def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torch.Tensor,
            scaling_modifier=1.0, override_color=None, stage="fine", return_decomposition=False, return_dx=False,
-           render_feat=False, densify_accum=None):
+           render_feat=False, densify_accum=None, extra_colors=None):
     """Mirror of gaussian_renderer/__init__.py::render.  `viewpoint_camera` is a dict with the fields the reference
     reads from a Camera (image_height/width, FoVx/FoVy or tanfovx/tanfovy, world_view_transform=viewmatrix,
     full_proj_transform=projmatrix, camera_center=campos, time).
     densify_accum (extension): (xyz_gradient_accum, denom, max_radii2D) updated by the rasterizer's backward itself when the
     RGB + feature pair runs as one node (train.py:489-493 otherwise does it in separate passes); the result dict then carries
-    "densify_stats_fused": True."""
+    "densify_stats_fused": True.
+    extra_colors (extension, no_grad only): a sequence of [P,3] colour tensors.  After the frame's own rasterisation each one is
+    blended on the SAME geometry tensors, so the rasterizer's geometry cache serves it without another preprocess / binning / sort
+    (s3g_raster_forward_reuse); the images come back as out["extra"], a list of [3,H,W].  What the reference does with one more
+    `render(..., override_color=c)` per image (utils/video_utils.py:267,284), on the fused route and the frame's own geometry."""
+    if extra_colors is not None and torch.is_grad_enabled():
+        raise RuntimeError("render(extra_colors=...) is an inference extension: call it under torch.no_grad()")
     dev = pc.get_xyz.device
     # the reference builds `zeros_like(xyz, requires_grad=True) + 0` and retain_grad()s it (:31-35): a fill, an add and a
     # non-leaf whose .grad its caller reads.  Nothing ever reads the VALUES of means2D (it only carries the viewspace gradient),
@@ -548,6 +555,15 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
             out["dshs_l1"] = dshs_l1
     if plane_reg is not None:
         out["plane_reg"] = plane_reg
+    if extra_colors is not None:
+        P = means3D_final.shape[0]
+        extra = []
+        for c in extra_colors:
+            if not torch.is_tensor(c) or tuple(c.shape) != (P, 3) or c.device != means3D_final.device:
+                raise RuntimeError(f"render: every entry of extra_colors must be a [{P},3] tensor on the Gaussians' device")
+            extra.append(rasterizer(means3D=means3D_final, means2D=means2D, shs=None, colors_precomp=c, opacities=opacity,
+                                    scales=scales_final, rotations=rotations_final, cov3D_precomp=cov3D_precomp)[0])
+        out["extra"] = extra
     return out
 
 
@@ -619,6 +635,77 @@ def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: 
     return {"psnr": non_zero_mean(per_frame[:, _metrics.PSNR]), "ssim": non_zero_mean(per_frame[:, _metrics.SSIM]),
             "masked_psnr": non_zero_mean(per_frame[contributed, _metrics.MASKED_PSNR]),
             "masked_ssim": non_zero_mean(per_frame[contributed, _metrics.MASKED_SSIM]), "per_frame": per_frame}
+
+
+@torch.no_grad()
+def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.Tensor, num_cams: int = 3, sink=None,
+                 with_rgb: bool = False) -> Dict:
+    """The forward and backward scene-flow images of the reference's evaluation loop (utils/video_utils.py:203-209, 252-299): frame t,
+    rendered in stage "fine" at its own camera and time, painted with C(dx[t + n] - dx[t]) and C(dx[t] - dx[t - n]) (flow.frame_plan,
+    n = num_cams; C = flow.scene_flow_colors).  `cameras` in dataset order: num_cams cameras per timestamp.
+
+    Where the reference keeps dx of every frame, evaluates the colours per image through the host and pays a whole render -- plain
+    PyTorch deformation, preprocess, binning, sort -- per image:
+      * dx is evaluated once per distinct cam["time"] (net.deform_heads, one timestamp ahead of the frames being rendered); the frame's
+        own render() then finds that evaluation in the inference cache.  At most three timestamps' dx are alive (and two cached
+        evaluations: the current timestamp's and the next one's);
+      * the colours are evaluated once per distinct (time_a, time_b) and serve every camera of both timestamps, as the forward flow of
+        the earlier and the backward flow of the later;
+      * both images of a frame come from ONE render(..., extra_colors=[ff, bf]): one geometry, two more blend passes.
+
+    -> {"forward_flows": [...], "backward_flows": [...]} (+ "rgbs" with with_rgb=True): one [3,H,W] device tensor per frame.  The
+    reference's lists hold `image.permute(1, 2, 0).cpu().numpy()` of the same images ([H,W,3]).
+    sink(kind, frame_index, image), kind in ("forward", "backward", "rgb"): every image is handed over as soon as it exists and none
+    is kept (the lists come back empty): 150 frames x 2 x 20 MB need not stay resident.
+    Needs the fused deformation route (the reference's default head configuration, SH degree 3, on the GPU): there is no second
+    implementation behind it."""
+    from . import flow as _flow
+    forward_plan, backward_plan = _flow.frame_plan(len(cameras), num_cams)
+    net = pc._deformation.deformation_net
+    xyz = pc.get_xyz
+    if not (xyz.is_cuda and net._fused_ok() and pc.max_sh_degree == 3 and getattr(pipe, "convert_SHs_python", True)
+            and getattr(pipe, "fused_glue", True)):
+        raise RuntimeError("render_flows needs the fused deformation route: GPU tensors, the default head configuration "
+                           "(dx + dshs + feature head), SH degree 3, convert_SHs_python and fused_glue on")
+    dev = xyz.device
+    times = [float(cam["time"]) for cam in cameras]
+    window: Dict[float, torch.Tensor] = {}      # timestamp -> dx
+    entries: Dict[float, object] = {}           # timestamp -> the deformation's cached evaluation (dx, dshs) of it
+    colors: Dict[tuple, torch.Tensor] = {}      # (time_a, time_b) -> C(dx[time_b] - dx[time_a])
+    result = {"forward_flows": [], "backward_flows": []}
+    if with_rgb:
+        result["rgbs"] = []
+
+    def deliver(kind, key, i, image):
+        if sink is not None:
+            sink(kind, i, image)
+        else:
+            result[key].append(image)
+
+    for i, cam in enumerate(cameras):
+        pairs = [(times[p.from_frame], times[p.to_frame]) for p in (forward_plan[i], backward_plan[i])]
+        needed = {t for pair in pairs for t in pair} | {times[i]}
+        for t in [t for t in window if t not in needed]:
+            del window[t]
+            entries.pop(t, None)
+        for key in [key for key in colors if key[0] not in needed or key[1] not in needed]:
+            del colors[key]
+        for t in sorted(needed - set(window), key=lambda t: t == times[i]):      # the frame's own timestamp last: its entry stays installed
+            window[t] = net.deform_heads(xyz, _uniform_time(t, dev), uniform_time=True, reg_weights=None, need_feat=False)[0]
+            entries[t] = net.inference_cache_entry()
+        net.install_inference_cache(entries.get(times[i]))
+        for pair in pairs:
+            if pair not in colors:
+                colors[pair] = _flow.scene_flow_colors(window[pair[0]], window[pair[1]])
+        unique = [colors[pairs[0]]] + ([colors[pairs[1]]] if pairs[1] != pairs[0] else [])
+        pkg = render(cam, pc, pipe, bg, stage="fine", extra_colors=unique)
+        if with_rgb:
+            deliver("rgb", "rgbs", i, pkg["render"])
+        deliver("forward", "forward_flows", i, pkg["extra"][0])
+        deliver("backward", "backward_flows", i, pkg["extra"][-1])
+        if i + 1 == len(cameras) or times[i + 1] != times[i]:
+            entries[times[i]] = None             # the timestamp's frames are done: only its dx is still needed, not its dshs
+    return result
 
 
 _weight_cache: Dict = {}
