@@ -25,17 +25,10 @@ def test_glue_matches_reference_golden(gpu_device):
     np.testing.assert_allclose(cols.cpu().numpy(), gl["colors"], rtol=2e-5, atol=2e-6)
 
 
-@pytest.mark.parametrize("live", [1.0, 0.3, 0.15])
-@pytest.mark.parametrize("deg", [0, 1, 2, 3])
-@pytest.mark.parametrize("with_dshs", [True, False])
-def test_glue_forward_backward_vs_restatement(gpu_device, deg, with_dshs, live):
-    """live: fraction of the Gaussians whose colour receives a gradient (a view sees ~18 % of them).  The backward stages the
-    coefficient rows of up to 64 live Gaussians per workgroup through LDS (csrc/glue.hip, round 6): 0.15 = every live row staged,
-    0.3 = staged rows and per-lane rows in one workgroup, 1.0 = mostly per-lane rows."""
+def _glue_forward_backward_vs_restatement(gpu_device, deg, with_dshs, live, P):
     from oracle import hexplane_ref as hr
     from s3gaussian_amd.glue import activations_and_colors
     g = torch.Generator().manual_seed(10 * deg + int(with_dshs))
-    P = 1000
     mk = lambda *s: torch.randn(*s, generator=g)
     f_dc, f_rest, dshs, xyz = mk(P, 1, 3), 0.3 * mk(P, 15, 3), 0.1 * mk(P, 16, 3), 3 * mk(P, 3)
     ls, rr, ol, campos = 0.5 * mk(P, 3), mk(P, 4), mk(P, 1), torch.tensor([0.3, -0.2, 1.1])
@@ -72,6 +65,27 @@ def test_glue_forward_backward_vs_restatement(gpu_device, deg, with_dshs, live):
             assert float(a.grad.abs().max()) == 0.0
             continue
         assert rel_l2(a.grad.cpu().numpy(), b.grad.numpy()) < 1e-5, i
+
+
+@pytest.mark.parametrize("live", [1.0, 0.3, 0.15])
+@pytest.mark.parametrize("deg", [0, 1, 2, 3])
+@pytest.mark.parametrize("with_dshs", [True, False])
+def test_glue_forward_backward_vs_restatement(gpu_device, deg, with_dshs, live):
+    """live: fraction of the Gaussians whose colour receives a gradient (a view sees ~18 % of them); the others carry a zero colour
+    gradient through the same code.  glue_backward_kernel (csrc/glue.hip) treats every Gaussian of its 256-row block alike: each
+    thread stages its Gaussian's 16 basis values and 3 clamped colour gradients in LDS (19 floats), then the workgroup writes the
+    g_f_dc / g_f_rest / g_dshs rows of the block -- the outer products basis[k] * dRGB[c], plus the sign term of mean|dshs| -- as
+    contiguous sweeps.  P = 1000 is three full blocks and one of 232 rows."""
+    _glue_forward_backward_vs_restatement(gpu_device, deg, with_dshs, live, 1000)
+
+
+@pytest.mark.parametrize("P", [1, 255, 256, 257])
+@pytest.mark.parametrize("with_dshs", [True, False])
+def test_glue_forward_backward_vs_restatement_block_edges(gpu_device, with_dshs, P):
+    """Block edges at degree 3: one row (P = 1), one row short of a block (255: the forward's ragged staging walk
+    glue_stage_rows<false> with its run-time trip counts, the backward's partial sweeps), exactly one block (256: only
+    glue_stage_rows<true>) and a full block followed by a one-row block (257).  Same bars as the P = 1000 test."""
+    _glue_forward_backward_vs_restatement(gpu_device, 3, with_dshs, 1.0, P)
 
 
 def test_render_fused_and_unfused_paths_agree(gpu_device):

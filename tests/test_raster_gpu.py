@@ -28,9 +28,9 @@ def oracle():
     return RasterOracle(np.float32)
 
 
-def run_gpu(s, dev, mode="precomp", sh_degree=3, debug=False, grads=None, cov3D=None, seed_grad=5):
+def run_gpu(s, dev, mode="precomp", sh_degree=3, debug=False, grads=None, cov3D=None, seed_grad=5, scale_modifier=1.0):
     from diff_gaussian_rasterization import GaussianRasterizer
-    rs = settings_from(s, dev, sh_degree=sh_degree if mode == "sh" else 0, debug=debug)
+    rs = settings_from(s, dev, sh_degree=sh_degree if mode == "sh" else 0, debug=debug)._replace(scale_modifier=scale_modifier)
     rast = GaussianRasterizer(raster_settings=rs)
     t = lambda x: x.to(dev).clone().requires_grad_(True)
     means3D, op = t(s["means3D"]), t(s["opacities"])
@@ -90,6 +90,33 @@ def test_forward_backward_vs_oracle(gpu_device, oracle, mode, shape):
     gc, gd = grad_pair(H, W)
     gpu = run_gpu(s, gpu_device, mode=mode)
     ref = oracle_forward(oracle, s, mode=mode)
+    bad = check_forward(gpu, ref, H, W)
+    rb = oracle.backward(ref, *backprop_masked(gpu, gc, gd, bad, gpu_device))
+    L = gpu["leaves"]
+    assert rel_l2(L["means3D"].grad.cpu().numpy(), rb["dL_dmeans3D"]) <= GRAD_TOL
+    assert rel_l2(L["means2D"].grad.cpu().numpy(), rb["dL_dmeans2D"]) <= GRAD_TOL
+    assert rel_l2(L["opacities"].grad.cpu().numpy(), rb["dL_dopacity"]) <= GRAD_TOL
+    assert rel_l2(L["scales"].grad.cpu().numpy(), rb["dL_dscales"]) <= GRAD_TOL
+    assert rel_l2(L["rotations"].grad.cpu().numpy(), rb["dL_drotations"]) <= GRAD_TOL
+    if mode == "precomp":
+        assert rel_l2(L["colors"].grad.cpu().numpy(), rb["dL_dcolors"]) <= GRAD_TOL
+    else:
+        assert rel_l2(L["shs"].grad.cpu().numpy(), rb["dL_dsh"]) <= GRAD_TOL
+
+
+@pytest.mark.parametrize("mode", ["precomp", "sh"])
+@pytest.mark.parametrize("modifier", [0.6, 1.7])
+def test_scale_modifier_vs_oracle(gpu_device, oracle, modifier, mode):
+    """scale_modifier != 1 (render(scaling_modifier=...), every caller of the training path passes 1.0): the forward kernel scales the
+    3-D covariance by it, the backward multiplies dL/dscales by it (computeCov3D, forward.cu:118-124, backward.cu:278-331).  The modifier reaches
+    both sides as a plain argument; same bars as test_forward_backward_vs_oracle."""
+    W, H = 48, 40
+    s = tiny_scene(P=400, W=W, H=H, seed=1)
+    gc, gd = grad_pair(H, W)
+    gpu = run_gpu(s, gpu_device, mode=mode, scale_modifier=modifier)
+    ref = oracle_forward(oracle, s, mode=mode, scale_modifier=modifier)
+    plain = oracle_forward(oracle, s, mode=mode)
+    assert not np.array_equal(ref["radii"], plain["radii"])        # the modifier does something on this scene
     bad = check_forward(gpu, ref, H, W)
     rb = oracle.backward(ref, *backprop_masked(gpu, gc, gd, bad, gpu_device))
     L = gpu["leaves"]
