@@ -6,12 +6,14 @@
   training_step()     <- train.py:372-437,521-522 for one view (batch_size = 1)
   evaluate()          <- the metric part of utils/video_utils.py:169-241 (PSNR, SSIM and their masked forms per frame, metrics.py)
   render_flows()      <- the flow part of utils/video_utils.py:203-209, 252-299 (forward / backward scene-flow images, flow.py)
+  evaluate_video()    <- utils/video_utils.py:116-349 + 439-499 in one pass: metrics, decomposition, flows and the uint8 strips the
+                         reference hands to its video writer, from ONE render per camera (frames.py)
 
 Adaptive density control -- GaussianParams.densify / prune / reset_opacity and the schedule of train.py:494-516 -- lives in
 density.py on kernels of its own (include/s3g_density.h).  Everything else outside that path (data readers, checkpoints'
-surroundings, LPIPS and the video files of the evaluation, logging) stays with the reference and is NOT rebuilt here (SURVEY.md
-section 2, DESIGN.md "out of scope").  The losses are plain PyTorch on the GPU exactly like the reference's utils/loss_utils.py;
-the operators underneath are the HIP library.
+surroundings, LPIPS and the video encoder of the evaluation -- its frames are built here --, logging) stays with the reference and
+is NOT rebuilt here (DESIGN.md "out of scope").  The losses are plain PyTorch on the GPU exactly like the
+reference's utils/loss_utils.py; the operators underneath are the HIP library.
 """
 from __future__ import annotations
 
@@ -637,9 +639,16 @@ def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: 
             "masked_ssim": non_zero_mean(per_frame[contributed, _metrics.MASKED_SSIM]), "per_frame": per_frame}
 
 
+def _fused_route(pc: GaussianParams, pipe: SimpleNamespace) -> bool:
+    """render() takes the fused deformation route for this model: GPU tensors, the default head configuration, SH degree 3,
+    convert_SHs_python and fused_glue on."""
+    return bool(pc.get_xyz.is_cuda and pc._deformation.deformation_net._fused_ok() and pc.max_sh_degree == 3
+                and getattr(pipe, "convert_SHs_python", True) and getattr(pipe, "fused_glue", True))
+
+
 @torch.no_grad()
 def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.Tensor, num_cams: int = 3, sink=None,
-                 with_rgb: bool = False) -> Dict:
+                 with_rgb: bool = False, return_decomposition: bool = False, on_frame=None) -> Dict:
     """The forward and backward scene-flow images of the reference's evaluation loop (utils/video_utils.py:203-209, 252-299): frame t,
     rendered in stage "fine" at its own camera and time, painted with C(dx[t + n] - dx[t]) and C(dx[t] - dx[t - n]) (flow.frame_plan,
     n = num_cams; C = flow.scene_flow_colors).  `cameras` in dataset order: num_cams cameras per timestamp.
@@ -657,14 +666,16 @@ def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.T
     reference's lists hold `image.permute(1, 2, 0).cpu().numpy()` of the same images ([H,W,3]).
     sink(kind, frame_index, image), kind in ("forward", "backward", "rgb"): every image is handed over as soon as it exists and none
     is kept (the lists come back empty): 150 frames x 2 x 20 MB need not stay resident.
+    return_decomposition is passed on to each frame's render(); on_frame(i, pkg) is called with frame i's full render result (its
+    "extra" holds the forward flow image first and the backward one last) before the images are delivered: evaluate_video hangs the
+    rest of the evaluation on the same render this way.
     Needs the fused deformation route (the reference's default head configuration, SH degree 3, on the GPU): there is no second
     implementation behind it."""
     from . import flow as _flow
     forward_plan, backward_plan = _flow.frame_plan(len(cameras), num_cams)
     net = pc._deformation.deformation_net
     xyz = pc.get_xyz
-    if not (xyz.is_cuda and net._fused_ok() and pc.max_sh_degree == 3 and getattr(pipe, "convert_SHs_python", True)
-            and getattr(pipe, "fused_glue", True)):
+    if not _fused_route(pc, pipe):
         raise RuntimeError("render_flows needs the fused deformation route: GPU tensors, the default head configuration "
                            "(dx + dshs + feature head), SH degree 3, convert_SHs_python and fused_glue on")
     dev = xyz.device
@@ -698,13 +709,156 @@ def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.T
             if pair not in colors:
                 colors[pair] = _flow.scene_flow_colors(window[pair[0]], window[pair[1]])
         unique = [colors[pairs[0]]] + ([colors[pairs[1]]] if pairs[1] != pairs[0] else [])
-        pkg = render(cam, pc, pipe, bg, stage="fine", extra_colors=unique)
+        pkg = render(cam, pc, pipe, bg, stage="fine", return_decomposition=return_decomposition, extra_colors=unique)
+        if on_frame is not None:
+            on_frame(i, pkg)
         if with_rgb:
             deliver("rgb", "rgbs", i, pkg["render"])
         deliver("forward", "forward_flows", i, pkg["extra"][0])
         deliver("backward", "backward_flows", i, pkg["extra"][-1])
         if i + 1 == len(cameras) or times[i + 1] != times[i]:
             entries[times[i]] = None             # the timestamp's frames are done: only its dx is still needed, not its dshs
+    return result
+
+
+VIDEO_KEYS = ("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs", "forward_flows", "backward_flows")
+_VIDEO_SOURCE = {"rgbs": "render", "depths": "depth", "dynamic_rgbs": "render_d", "static_rgbs": "render_s"}
+
+
+def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: torch.Tensor, masks=None, num_cams: int = 3,
+                   keys=("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs"), sink=None, host: bool = False,
+                   compute_metrics: bool = True, stage: str = "fine") -> Dict:
+    """The reference's evaluation loop with its videos' frames (utils/video_utils.py:116-349 render_func, then 439-499
+    save_seperate_videos) from ONE render per camera: render(cam, return_decomposition=<a decomposition key is asked for>,
+    extra_colors=<the frame's flow colours, if a flow key is asked for>) feeds metrics.image_metrics -- row i of the [N,5] table,
+    exactly as evaluate() fills it -- and one frames.compose call with one job per key, which writes camera (i % num_cams)'s tile of
+    timestamp (i // num_cams)'s strips; the fp32 images are dropped right after.
+
+    keys: any of VIDEO_KEYS.  A strip is the [H, num_cams * W, C] uint8 array the reference appends to the key's video writer for
+    one timestamp -- to8b of the cameras' images side by side; C = 1 for "depths", whose frames are each divided by their own maximum.
+    T = len(cameras) // num_cams timestamps; leftover cameras are rendered and counted in the metrics and appear in no strip.
+    When a timestamp's last camera has been composed each of its strips goes to sink(key, timestamp_index, strip), in the order of
+    `keys`; without a sink into result["frames"][key] (with one, those lists stay empty).  result["middle"][key] is the strip of
+    timestamp T // 2, the reference's return_frame_dict.
+    host=True: the strips arrive as numpy arrays, through two pinned slots per key filled with non_blocking copies: timestamp i is
+    handed over after the work of timestamp i + 1 has been enqueued (the last one at the end), behind an event that has long fired by
+    then, so no frame waits for the device.  A sink receives a view of the pinned slot, valid until it returns (what a video
+    writer's append_data needs); the lists and "middle" hold copies.
+    -> {"psnr", "ssim", "masked_psnr", "masked_ssim", "per_frame"} as evaluate() (-1 / None with compute_metrics=False),
+    "frames", "middle", "num_timestamps".  LPIPS, file names and the encoder stay with the caller.
+    Flow keys run the loop through render_flows (its windowing of dx and colours; stage "fine", at least 2 * num_cams cameras); they
+    and the decomposition keys need the fused deformation route, as render_flows does."""
+    from . import frames as _frames
+    keys = tuple(keys)
+    unknown = [k for k in keys if k not in VIDEO_KEYS]
+    if unknown or not keys or len(set(keys)) != len(keys) or len(keys) > _frames.MAX_JOBS:
+        raise RuntimeError(f"evaluate_video: keys must be distinct entries of {VIDEO_KEYS} (got {keys})")
+    n, N = int(num_cams), len(cameras)
+    if n == 5:
+        raise RuntimeError("evaluate_video: num_cams = 5 is refused: the reference rescales the two outer views of five with "
+                           "resize_five_views (a scipy spline zoom), which is deliberately not rebuilt here")
+    if n < 1:
+        raise RuntimeError(f"evaluate_video: num_cams = {num_cams}")
+    if len(gt_images) != N or (masks is not None and len(masks) != N):
+        raise RuntimeError("evaluate_video: one ground-truth image (and one mask entry) per camera")
+    want_flow = any(k in ("forward_flows", "backward_flows") for k in keys)
+    want_dec = any(k in ("dynamic_rgbs", "static_rgbs") for k in keys)
+    if (want_flow or want_dec) and not (_fused_route(pc, pipe) and "fine" in stage):
+        raise RuntimeError("evaluate_video: the decomposition and flow keys need the fused deformation route in a fine stage: GPU "
+                           "tensors, the default head configuration (dx + dshs + feature head), SH degree 3, convert_SHs_python "
+                           "and fused_glue on")
+    if want_flow and stage != "fine":
+        raise RuntimeError('evaluate_video: the flow keys are rendered by render_flows, in stage "fine"')
+    dev = pc.get_xyz.device
+    T = N // n
+    table = torch.empty((N, _metrics.RECORD), dtype=torch.float64, device=dev) if compute_metrics else None
+    result = {"frames": {k: [] for k in keys}, "middle": {}, "num_timestamps": T}
+    normalize = [k == "depths" for k in keys]
+    state = SimpleNamespace(strips=None, size=None, pending=None, ring={})
+
+    def hand_over(t, strips):                  # device strips, or views of the pinned slots
+        for k, s in zip(keys, strips):
+            if t == T // 2:
+                result["middle"][k] = s.copy() if host else s
+            if sink is not None:
+                sink(k, t, s)
+            else:
+                result["frames"][k].append(s.copy() if host else s)
+
+    def drain(pending):
+        if pending is not None:
+            t, event, slots = pending
+            event.synchronize()                # recorded one timestamp of work ago
+            hand_over(t, [s.numpy() for s in slots])
+
+    def finish_timestamp(t):
+        if not host:
+            hand_over(t, state.strips)
+            return
+        slots = []
+        for k, s in zip(keys, state.strips):
+            ring = state.ring.get(k)
+            if ring is None or ring[0].shape != s.shape:
+                ring = state.ring[k] = [torch.empty(s.shape, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            slots.append(ring[t % 2])          # timestamp t - 2 left this slot when t - 1's work was enqueued
+            slots[-1].copy_(s, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        previous, state.pending = state.pending, (t, event, slots)
+        drain(previous)                        # timestamp t - 1: everything of t is enqueued behind it
+
+    def on_frame(i, pkg):
+        H, W = int(pkg["render"].shape[1]), int(pkg["render"].shape[2])
+        gt = gt_images[i]
+        if not torch.is_tensor(gt) or tuple(gt.shape) != (3, H, W):
+            raise RuntimeError(f"evaluate_video: gt_images[{i}] must be a [3,{H},{W}] tensor "
+                               f"(got {tuple(gt.shape) if torch.is_tensor(gt) else type(gt).__name__})")
+        if compute_metrics:
+            _metrics.image_metrics(pkg["render"], gt, None if masks is None else masks[i], out=table[i])
+        t, c = divmod(i, n)
+        if t >= T:
+            return
+        if c == 0:
+            state.size = (H, W)
+            state.strips = [torch.empty(_frames.strip_shape(H, W, 1 if k == "depths" else 3, n), dtype=torch.uint8, device=dev)
+                            for k in keys]
+        elif state.size != (H, W):
+            raise RuntimeError(f"evaluate_video: camera {i} renders {H} x {W}, the first camera of its timestamp "
+                               f"{state.size[0]} x {state.size[1]}: one strip holds images of one size")
+        images = []
+        for k in keys:
+            if k == "gt_rgbs":
+                images.append(gt)
+            elif k == "forward_flows":
+                images.append(pkg["extra"][0])
+            elif k == "backward_flows":
+                images.append(pkg["extra"][-1])
+            else:
+                if _VIDEO_SOURCE[k] not in pkg:
+                    raise RuntimeError(f'evaluate_video: render() returned no "{_VIDEO_SOURCE[k]}" for key "{k}" on this route')
+                images.append(pkg[_VIDEO_SOURCE[k]])
+        _frames.compose(images, state.strips, c, normalize=normalize)
+        if c == n - 1:
+            finish_timestamp(t)
+            state.strips = None
+
+    with torch.no_grad():
+        if want_flow:
+            render_flows(pc, cameras, pipe, bg, num_cams=n, sink=lambda kind, i, image: None, return_decomposition=want_dec,
+                         on_frame=on_frame)
+        else:
+            for i, cam in enumerate(cameras):
+                on_frame(i, render(cam, pc, pipe, bg, stage=stage, return_decomposition=want_dec))
+        drain(state.pending)
+    if not compute_metrics:
+        result.update({"psnr": -1, "ssim": -1, "masked_psnr": -1, "masked_ssim": -1, "per_frame": None})
+        return result
+    per_frame = table.cpu()
+    non_zero_mean = lambda x: float(x.sum() / len(x)) if len(x) > 0 else -1      # video_utils.py:44-46
+    contributed = per_frame[:, _metrics.MASKED_PIXELS] > 0
+    result.update({"psnr": non_zero_mean(per_frame[:, _metrics.PSNR]), "ssim": non_zero_mean(per_frame[:, _metrics.SSIM]),
+                   "masked_psnr": non_zero_mean(per_frame[contributed, _metrics.MASKED_PSNR]),
+                   "masked_ssim": non_zero_mean(per_frame[contributed, _metrics.MASKED_SSIM]), "per_frame": per_frame})
     return result
 
 
