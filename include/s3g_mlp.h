@@ -40,7 +40,12 @@ size_t s3g_deform_mlp_pack_bytes(void);
 /* features [P,128] -> dx [P,3], dshs [P,48], feat [P,3].  `stash`: device scratch of s3g_deform_mlp_stash_bytes(P)
  * bytes when save_activations != 0 (a backward will follow), else at least s3g_deform_mlp_pack_bytes().
  * feat may be NULL when save_activations == 0: the feature (dino) head is then skipped -- a render that does not draw the
- * feature image (gaussian_renderer/__init__.py:153, render_feat=False) has no use for it. */
+ * feature image (gaussian_renderer/__init__.py:153, render_feat=False) has no use for it.
+ * dx may be NULL (static scenes, ModelHiddenParams no_dx=True: scene/deformation.py:119-121 never calls the head): the position
+ * head is skipped -- P1, its ReLU, P2 and the dx store are not computed, and with save_activations != 0 stash plane 1 (pos1) and
+ * mask word 1 of every tile are left unwritten.  dshs, feat and every other stash plane / mask word are bit for bit what the call
+ * writes with a non-NULL dx.  Combines with feat == NULL (then save_activations must be 0, as above).  w->P1..pb2 stay valid
+ * pointers in every case: the weight images are packed whole. */
 int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const float* features, float* dx, float* dshs, float* feat,
                            float* stash, int save_activations, void* stream);
 
@@ -48,7 +53,10 @@ int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const float* features
  * gradients in `gw` (ACCUMULATED: the caller zero-fills them).  `stash` from the matching forward (weights must be
  * unchanged since); `workspace` of 5 * P * 64 * 4 bytes, uninitialised.
  * g_feat may be NULL = the feature output received no gradient (the feature image is not in the loss): the dino head's
- * backward is skipped and gw->D0..db2 are left untouched, like autograd leaving those parameters' .grad at None. */
+ * backward is skipped and gw->D0..db2 are left untouched, like autograd leaving those parameters' .grad at None.
+ * g_dx may be NULL = the forward ran with dx == NULL: the position head's backward is skipped -- no read of g_dx, of mask word 1 or of
+ * stash plane 1, workspace plane 2 (the pos1 signal) is not written -- and gw->P1, pb1, P2, pb2 are left untouched and may be NULL.
+ * All four combinations of g_dx / g_feat being NULL or not are valid (s3g_deform_mlp_backward_ordered alike). */
 int s3g_deform_mlp_backward(const s3g_mlp_params* w, int P, const float* features, const float* stash, const float* g_dx,
                             const float* g_dshs, const float* g_feat, float* g_features, const s3g_mlp_params* gw,
                             float* workspace, void* stream);

@@ -13,6 +13,7 @@
 //                        activations are stashed for the backward with 16-byte stores, their ReLU masks as bit words.
 //   mlp_backward_kernel  the per-point chain (transposed-weight reads of the same image + the ReLU mask words) ->
 //                        g_features and 5 gradient signals, same register-resident scheme.
+//   mlp_static_*         the six chain kernels without the position head (static scenes, no_dx: dx / g_dx == NULL)
 //   <SPLIT = false>      exact fp32 (v_mfma_f32_32x32x2_f32: 64 FLOP/clk/SIMD) -- S3G_MLP_F32;
 //   <SPLIT = true>       every operand split into three bf16 pieces on the fly (v_mfma_f32_32x32x16_bf16, fp32 accuracy) --
 //                        S3G_MLP_BF16X3_ONTHEFLY, the checker of:
@@ -60,8 +61,12 @@ struct MlpFwdArgs {
   uint32_t* maskbits;  // [tiles][5][64] ReLU mask words (NULL when no backward follows)
 };
 
-template <bool SPLIT>
-__global__ void __launch_bounds__(NWAVE * 64) mlp_forward_kernel(const MlpFwdArgs a) {
+// The forward kernels are thin __global__ wrappers of body templates with one more argument, POS.  <POS = false>: the position head
+// is compiled out (static scenes, no_dx: a.dx == NULL) -- stash plane 1 and mask word 1 stay unwritten.  The mlp_static_forward_*
+// kernels are those instantiations; the kernels of the default configuration keep their names and their machine code
+// (profiles/mlp_static_isa_identity.txt).
+template <bool SPLIT, bool POS>
+__device__ __forceinline__ void mlp_forward_body(const MlpFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   load_weights(lds, a.packed, wave, lane);
@@ -105,6 +110,7 @@ __global__ void __launch_bounds__(NWAVE * 64) mlp_forward_kernel(const MlpFwdArg
     uint32_t* mw = a.maskbits ? a.maskbits + (size_t)tile * 5 * 64 + ln : nullptr;
     if (a.stash) act_store<HID, 2, false>(hid, a.stash + 0 * PS, 0, p0, npts, ln);
     if (mw) mw[0 * 64] = pack_positive<2>(hid);
+    if constexpr (POS) {
     // pos head: dx = P2 relu(P1 relu(hidden) + pb1) + pb2
     acc_bias<2>(act, BIAS(1), ln);
     gemm_fw<SPLIT, 2, 2, true>(WSLAB(2), 65, hid, act, ln);
@@ -119,6 +125,7 @@ __global__ void __launch_bounds__(NWAVE * 64) mlp_forward_kernel(const MlpFwdArg
       float o3[3];
       head3_fw(WSLAB(4), BIAS(3), act, o3, ln);
       store3(o3, a.dx, p0, npts, ln);
+    }
     }
     // shs head: dshs = S2 relu(S1 relu(hidden) + sb1) + sb2
     acc_bias<2>(act, BIAS(2), ln);
@@ -155,6 +162,10 @@ __global__ void __launch_bounds__(NWAVE * 64) mlp_forward_kernel(const MlpFwdArg
     cur = nxt;   // copies at the very end: the prefetch has had the whole tile to land
   }
 }
+template <bool SPLIT>
+__global__ void __launch_bounds__(NWAVE * 64) mlp_forward_kernel(const MlpFwdArgs a) { mlp_forward_body<SPLIT, true>(a); }
+template <bool SPLIT>
+__global__ void __launch_bounds__(NWAVE * 64) mlp_static_forward_kernel(const MlpFwdArgs a) { mlp_forward_body<SPLIT, false>(a); }
 
 struct MlpBwdArgs {
   int P;
@@ -171,6 +182,7 @@ struct BwdIn {
   float4 gs[6];       // g_dshs columns 8q + 4h .. +3 (q = 0..3) and 32 + 8q + 4h .. +3 (q = 0, 1): the 48 live columns
   uint32_t bits[5];
 };
+
 
 // Per-point backward chain, same register-resident scheme with the transposed weight reads.
 template <bool SPLIT>
@@ -251,6 +263,83 @@ __global__ void __launch_bounds__(NWAVE * 64) mlp_backward_kernel(const MlpBwdAr
     masked_bits<2, true>(ghid, acc, cur.bits[0]);
     act_store<HID, 2, false>(ghid, a.ws + 4 * PS, 0, p0, npts, lane);
     // ---- feature_out: g_x[:, half] = W0[:, half]^T ghid ----
+    acc_zero<2>(acc);
+    gemm_bw<SPLIT, 2, 2>(WSLAB(0), 65, ghid, acc, lane);
+    act_store<FEAT, 2, false>(acc, a.g_x, 0, p0, npts, lane);
+    acc_zero<2>(acc);
+    gemm_bw<SPLIT, 2, 2>(WSLAB(1), 65, ghid, acc, lane);
+    act_store<FEAT, 2, false>(acc, a.g_x, 64, p0, npts, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    cur = nxt;
+  }
+}
+
+// The same chain without the position head (static scenes, no_dx: a.g_dx == NULL): g_dx, mask word 1 and the pos1 plane are not read,
+// workspace plane 2 is not written.  Its own function, not an instantiation of a shared body: behind a common body the kernels above
+// lose their machine code (two instructions, operand orders), and the default configuration's kernels do not change for this one
+// (profiles/mlp_static_isa_identity.txt).  What it computes is mlp_backward_kernel with g_dx = 0, checked bit for bit
+// (tests/test_static_mlp_gpu.py).
+template <bool SPLIT>
+__global__ void __launch_bounds__(NWAVE * 64) mlp_static_backward_kernel(const MlpBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  load_weights(lds, a.packed, wave, lane);
+  const int ntiles = (a.P + MT - 1) / MT;
+  const size_t PS = (size_t)a.P * HID;
+  const int j = lane & 31, h = lane >> 5;
+  const bool dino = a.g_feat != nullptr;
+  auto issue = [&](BwdIn& I, int tile) {   // (I.gd and I.bits[1] stay unset: nothing reads them)
+    const size_t p = (size_t)min(tile * MT + j, a.P - 1);
+    const uint32_t* mw = a.maskbits + (size_t)tile * 5 * 64 + lane;
+#pragma unroll
+    for (int k = 0; k < 5; k++)
+      if (k != 1) I.bits[k] = mw[k * 64];
+#pragma unroll
+    for (int k = 0; k < 3; k++) I.gf[k] = dino ? a.g_feat[p * 3 + k] : 0.f;
+    const float* row = a.g_dshs + p * 48 + 4 * h;
+#pragma unroll
+    for (int c = 0; c < 6; c++) I.gs[c] = *reinterpret_cast<const float4*>(row + 8 * c);
+  };
+  const int stride = gridDim.x * NWAVE, t0 = blockIdx.x * NWAVE + wave;
+  BwdIn cur, nxt;
+  if (t0 < ntiles) issue(cur, t0);
+  for (int tile = t0; tile < ntiles; tile += stride) {
+    issue(nxt, min(tile + stride, ntiles - 1));
+    __builtin_amdgcn_sched_barrier(0);
+    const int p0 = tile * MT, npts = min(MT, a.P - p0);
+    f32x16 ghid[2], g[2], acc[2], g3[1];
+    acc_zero<2>(ghid);
+    if (dino) {
+      acc_zero<1>(g3);
+#pragma unroll
+      for (int k = 0; k < 3; k++) g3[0][k] = h == 0 ? cur.gf[k] : 0.f;
+      acc_zero<2>(acc);
+      gemm_reg_t<2, 1, 3>(WSLAB(8), 33, g3, acc, lane);              // D2^T g_feat
+      masked_bits<2, false>(g, acc, cur.bits[4]);
+      act_store<HID, 2, false>(g, a.ws + 0 * PS, 0, p0, npts, lane);
+      acc_zero<2>(acc);
+      gemm_bw<SPLIT, 2, 2>(WSLAB(7), 65, g, acc, lane);               // D1^T
+      masked_bits<2, false>(g, acc, cur.bits[3]);
+      act_store<HID, 2, false>(g, a.ws + 1 * PS, 0, p0, npts, lane);
+      gemm_bw<SPLIT, 2, 2>(WSLAB(6), 65, g, ghid, lane);              // ghid = D0^T
+    }
+    acc_zero<2>(acc);                                                // (where the position head's P1^T term would have started the sum)
+    {
+      f32x16 gs[2], t[2];
+#pragma unroll
+      for (int c = 0; c < 8; c++) {
+        const float4 v = c < 6 ? cur.gs[c < 6 ? c : 0] : make_float4(0.f, 0.f, 0.f, 0.f);
+        gs[c >> 2][4 * (c & 3) + 0] = v.x; gs[c >> 2][4 * (c & 3) + 1] = v.y;
+        gs[c >> 2][4 * (c & 3) + 2] = v.z; gs[c >> 2][4 * (c & 3) + 3] = v.w;
+      }
+      acc_zero<2>(t);
+      gemm_bw<SPLIT, 2, 2>(WSLAB(5), 65, gs, t, lane);                // S2^T g_dshs
+      masked_bits<2, false>(g, t, cur.bits[2]);
+    }
+    act_store<HID, 2, false>(g, a.ws + 3 * PS, 0, p0, npts, lane);
+    gemm_bw<SPLIT, 2, 2>(WSLAB(3), 65, g, acc, lane);                 // S1^T
+    masked_bits<2, true>(ghid, acc, cur.bits[0]);
+    act_store<HID, 2, false>(ghid, a.ws + 4 * PS, 0, p0, npts, lane);
     acc_zero<2>(acc);
     gemm_bw<SPLIT, 2, 2>(WSLAB(0), 65, ghid, acc, lane);
     act_store<FEAT, 2, false>(acc, a.g_x, 0, p0, npts, lane);
@@ -503,7 +592,105 @@ __global__ void __launch_bounds__(NWAVE * 64) mlp_backward_presplit_kernel(const
   }
 }
 
-__global__ void __launch_bounds__(NWAVE * 64) mlp_forward_presplit_kernel(const MlpFwdArgs a) {   // a.packed = the tpw image
+// mlp_backward_presplit_kernel without the position head: mlp_static_backward_kernel<true> with every fragment split ONCE (bit-identical
+// to it); its own function for the same reason.  The P1T / P2T regions of the image are loaded with the rest and not read.
+__global__ void __launch_bounds__(NWAVE * 64) mlp_static_backward_presplit_kernel(const MlpBwdArgs a) {   // a.packed = the tbw image
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const uint32_t* wsplit = reinterpret_cast<const uint32_t*>(lds);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = wave; c < tbw::WORDS / 256; c += NWAVE)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.packed + c * 256 + lane * 4),
+                                     (__attribute__((address_space(3))) void*)(lds + c * 256), 16, 0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const int ntiles = (a.P + MT - 1) / MT;
+  const size_t PS = (size_t)a.P * HID;
+  const int j = lane & 31, h = lane >> 5;
+  const bool dino = a.g_feat != nullptr;
+  auto issue = [&](BwdIn& I, int tile) {   // (I.gd and I.bits[1] stay unset: nothing reads them)
+    const size_t p = (size_t)min(tile * MT + j, a.P - 1);
+    const uint32_t* mw = a.maskbits + (size_t)tile * 5 * 64 + lane;
+#pragma unroll
+    for (int k = 0; k < 5; k++)
+      if (k != 1) I.bits[k] = mw[k * 64];
+#pragma unroll
+    for (int k = 0; k < 3; k++) I.gf[k] = dino ? a.g_feat[p * 3 + k] : 0.f;
+    const float* row = a.g_dshs + p * 48 + 4 * h;
+#pragma unroll
+    for (int c = 0; c < 6; c++) I.gs[c] = *reinterpret_cast<const float4*>(row + 8 * c);
+  };
+  const int stride = gridDim.x * NWAVE, t0 = blockIdx.x * NWAVE + wave;
+  BwdIn cur, nxt;
+  if (t0 < ntiles) issue(cur, t0);
+  for (int tile = t0; tile < ntiles; tile += stride) {
+    issue(nxt, min(tile + stride, ntiles - 1));
+    __builtin_amdgcn_sched_barrier(0);
+    const int p0 = tile * MT, npts = min(MT, a.P - p0);
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    f32x16 ghid[2], g[2], acc[2], g3[1];
+    ActSplit<2> gsp;
+    acc_zero<2>(ghid);
+    if (dino) {
+      acc_zero<1>(g3);
+#pragma unroll
+      for (int k = 0; k < 3; k++) g3[0][k] = h == 0 ? cur.gf[k] : 0.f;
+      acc_zero<2>(acc);
+      gemm_reg_t<2, 1, 3>(lds + tbw::D2T, tbw::H3LD, g3, acc, ln);          // D2^T g_feat: exact fp32 MFMAs
+      masked_bits<2, false>(g, acc, cur.bits[4]);
+      act_store<HID, 2, false>(g, a.ws + 0 * PS, 0, p0, npts, ln);
+      acc_zero<2>(acc);
+      act_split<2, false>(gsp, g);
+      gemm_split<2, 2>(wsplit + tbw::D1T, 4, 0, gsp, acc, ln);              // D1^T
+      masked_bits<2, false>(g, acc, cur.bits[3]);
+      act_store<HID, 2, false>(g, a.ws + 1 * PS, 0, p0, npts, ln);
+      act_split<2, false>(gsp, g);
+      gemm_split<2, 2>(wsplit + tbw::D0T, 4, 0, gsp, ghid, ln);             // ghid = D0^T
+    }
+    acc_zero<2>(acc);                                                      // (where the position head's P1^T term would have started the sum)
+    {
+      f32x16 gs[2], t[2];
+#pragma unroll
+      for (int c = 0; c < 8; c++) {
+        const float4 v = c < 6 ? cur.gs[c < 6 ? c : 0] : make_float4(0.f, 0.f, 0.f, 0.f);
+        gs[c >> 2][4 * (c & 3) + 0] = v.x; gs[c >> 2][4 * (c & 3) + 1] = v.y;
+        gs[c >> 2][4 * (c & 3) + 2] = v.z; gs[c >> 2][4 * (c & 3) + 3] = v.w;
+      }
+      acc_zero<2>(t);
+      ActSplit<2> ssp;
+      act_split<2, false>(ssp, gs);
+#pragma unroll
+      for (int ks = 0; ks < 3; ks++) {    // S2^T g_dshs: K = 48
+        Split8 aw[2];
+#pragma unroll
+        for (int mbo = 0; mbo < 2; mbo++)
+#pragma unroll
+          for (int pc = 0; pc < 3; pc++)
+            aw[mbo].p[pc] = *reinterpret_cast<const u32x4*>(wsplit + tbw::S2T + ((mbo * 3 + ks) * 3 + pc) * tbw::FRAG + ln * 4);
+#pragma unroll
+        for (int mbo = 0; mbo < 2; mbo++) t[mbo] = mfma_split(t[mbo], aw[mbo], ssp.b[ks >> 1][ks & 1]);
+      }
+      masked_bits<2, false>(g, t, cur.bits[2]);
+    }
+    act_store<HID, 2, false>(g, a.ws + 3 * PS, 0, p0, npts, ln);
+    act_split<2, false>(gsp, g);
+    gemm_split<2, 2>(wsplit + tbw::S1T, 4, 0, gsp, acc, ln);                // S1^T
+    masked_bits<2, true>(ghid, acc, cur.bits[0]);
+    act_store<HID, 2, false>(ghid, a.ws + 4 * PS, 0, p0, npts, ln);
+    act_split<2, false>(gsp, ghid);
+    acc_zero<2>(acc);
+    gemm_split<2, 2>(wsplit + tbw::W0T, 4, 0, gsp, acc, ln);
+    act_store<FEAT, 2, false>(acc, a.g_x, 0, p0, npts, ln);
+    acc_zero<2>(acc);
+    gemm_split<2, 2>(wsplit + tbw::W0T + 2 * 4 * 3 * tbw::FRAG, 4, 0, gsp, acc, ln);
+    act_store<FEAT, 2, false>(acc, a.g_x, 64, p0, npts, ln);
+    __builtin_amdgcn_sched_barrier(0);
+    cur = nxt;
+  }
+}
+
+template <bool POS>
+__device__ __forceinline__ void mlp_forward_presplit_body(const MlpFwdArgs a) {   // a.packed = the tpw image
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const uint32_t* wsplit = reinterpret_cast<const uint32_t*>(lds);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -571,6 +758,7 @@ __global__ void __launch_bounds__(NWAVE * 64) mlp_forward_presplit_kernel(const 
     if (a.stash) act_store<HID, 2, false>(hid, a.stash + 0 * PS, 0, p0, npts, ln);
     if (mw) mw[0 * 64] = pack_positive<2>(hid);
     act_split<2, true>(hs, hid);   // relu(hidden): the input of the position and SH heads
+    if constexpr (POS) {
     // pos head: dx = P2 relu(P1 relu(hidden) + pb1) + pb2.  P1 is fp32 in LDS: a lane's eight weights of a fragment are two 16-byte chunks of its row
     acc_bias<2>(act, bias(tpw::B_PB1), ln);
 #pragma unroll
@@ -590,6 +778,7 @@ __global__ void __launch_bounds__(NWAVE * 64) mlp_forward_presplit_kernel(const 
     acc_bias<1>(o, bias(tpw::B_PB2), ln);
     head3(tpw::P2, as, o, ln);
     act_store3(o, a.dx, p0, npts, ln);
+    }
     // shs head: dshs = S2 relu(S1 relu(hidden) + sb1) + sb2
     acc_bias<2>(act, bias(tpw::B_SB1), ln);
     gemm_split<2, 2>(wsplit + tpw::S1, 4, 0, hs, act, ln);
@@ -630,6 +819,8 @@ __global__ void __launch_bounds__(NWAVE * 64) mlp_forward_presplit_kernel(const 
     __builtin_amdgcn_sched_barrier(0);
   }
 }
+__global__ void __launch_bounds__(NWAVE * 64) mlp_forward_presplit_kernel(const MlpFwdArgs a) { mlp_forward_presplit_body<true>(a); }
+__global__ void __launch_bounds__(NWAVE * 64) mlp_static_forward_presplit_kernel(const MlpFwdArgs a) { mlp_forward_presplit_body<false>(a); }
 
 }  // namespace s3g
 
@@ -659,12 +850,15 @@ extern "C" int s3g_deform_mlp_get_arithmetic(void) { return g_mlp_arithmetic.loa
 static int mlp_set_attrs() {
   static std::atomic<uint64_t> done{0};
   if (device_needs_setup(done)) {
-    S3G_HIP_CHECK(hipFuncSetAttribute((const void*)mlp_forward_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_FLOATS * 4));
-    S3G_HIP_CHECK(hipFuncSetAttribute((const void*)mlp_backward_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_FLOATS * 4));
-    S3G_HIP_CHECK(hipFuncSetAttribute((const void*)mlp_forward_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_FLOATS * 4));
-    S3G_HIP_CHECK(hipFuncSetAttribute((const void*)mlp_backward_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_FLOATS * 4));
+    const void* exact[] = {(const void*)mlp_forward_kernel<false>,  (const void*)mlp_static_forward_kernel<false>,
+                           (const void*)mlp_backward_kernel<false>, (const void*)mlp_static_backward_kernel<false>,
+                           (const void*)mlp_forward_kernel<true>,   (const void*)mlp_static_forward_kernel<true>,
+                           (const void*)mlp_backward_kernel<true>,  (const void*)mlp_static_backward_kernel<true>};
+    for (const void* k : exact) S3G_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_FLOATS * 4));
     S3G_HIP_CHECK(hipFuncSetAttribute((const void*)mlp_forward_presplit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tpw::WORDS * 4));
+    S3G_HIP_CHECK(hipFuncSetAttribute((const void*)mlp_static_forward_presplit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tpw::WORDS * 4));
     S3G_HIP_CHECK(hipFuncSetAttribute((const void*)mlp_backward_presplit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tbw::WORDS * 4));
+    S3G_HIP_CHECK(hipFuncSetAttribute((const void*)mlp_static_backward_presplit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tbw::WORDS * 4));
     device_setup_done(done);
   }
   return S3G_OK;
@@ -672,7 +866,7 @@ static int mlp_set_attrs() {
 
 extern "C" int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const float* features, float* dx, float* dshs,
                                       float* feat, float* stash, int save_activations, void* stream_) {
-  if (!w || P < 0 || (P > 0 && (!features || !dx || !dshs || !stash || (!feat && save_activations)))) {
+  if (!w || P < 0 || (P > 0 && (!features || !dshs || !stash || (!feat && save_activations)))) {
     set_error("s3g_deform_mlp_forward: bad argument");
     return S3G_ERR_INVALID_ARG;
   }
@@ -686,6 +880,7 @@ extern "C" int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const floa
   const int ntiles = (P + MT - 1) / MT;
   const int blocks = min((ntiles + NWAVE - 1) / NWAVE, 256);
   const int arith = g_mlp_arithmetic.load(std::memory_order_relaxed);
+  const bool pos = dx != nullptr;   // dx == NULL: the kernels with the position head compiled out (static scenes, no_dx)
   // each arithmetic packs only the image its forward kernel reads: the pre-split one sits behind the slot of the fp32 one, which a
   // bf16x3 forward leaves unwritten (a backward in another mode packs the fp32 image itself)
   if (arith == S3G_MLP_BF16X3)
@@ -697,11 +892,15 @@ extern "C" int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const floa
   if (arith == S3G_MLP_BF16X3) {
     MlpFwdArgs s = a;
     s.packed = stash + PACK_FLOATS;
-    hipLaunchKernelGGL(mlp_forward_presplit_kernel, dim3(blocks), dim3(NWAVE * 64), tpw::WORDS * 4, stream, s);
-  } else if (arith == S3G_MLP_BF16X3_ONTHEFLY)
-    hipLaunchKernelGGL(mlp_forward_kernel<true>, dim3(blocks), dim3(NWAVE * 64), MLP_LDS_FLOATS * 4, stream, a);
-  else
-    hipLaunchKernelGGL(mlp_forward_kernel<false>, dim3(blocks), dim3(NWAVE * 64), MLP_LDS_FLOATS * 4, stream, a);
+    auto k = pos ? mlp_forward_presplit_kernel : mlp_static_forward_presplit_kernel;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(NWAVE * 64), tpw::WORDS * 4, stream, s);
+  } else if (arith == S3G_MLP_BF16X3_ONTHEFLY) {
+    auto k = pos ? mlp_forward_kernel<true> : mlp_static_forward_kernel<true>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(NWAVE * 64), MLP_LDS_FLOATS * 4, stream, a);
+  } else {
+    auto k = pos ? mlp_forward_kernel<false> : mlp_static_forward_kernel<false>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(NWAVE * 64), MLP_LDS_FLOATS * 4, stream, a);
+  }
   profile_end(S3G_PROFILE_MLP_FORWARD, stream, (double)P, 0.0);
   S3G_HIP_CHECK(hipGetLastError());
   return S3G_OK;
@@ -710,7 +909,7 @@ extern "C" int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const floa
 static int mlp_backward_impl(const s3g_mlp_params* w, int P, const float* features, const float* stash_, const float* g_dx,
                              const float* g_dshs, const float* g_feat, float* g_features, const s3g_mlp_params* gw, float* workspace,
                              float* partials, void* stream_) {
-  if (!w || !gw || P < 0 || (P > 0 && (!features || !stash_ || !g_dx || !g_dshs || !g_features || !workspace))) {
+  if (!w || !gw || P < 0 || (P > 0 && (!features || !stash_ || !g_dshs || !g_features || !workspace))) {
     set_error("s3g_deform_mlp_backward: bad argument");
     return S3G_ERR_INVALID_ARG;
   }
@@ -723,6 +922,7 @@ static int mlp_backward_impl(const s3g_mlp_params* w, int P, const float* featur
   const int ntiles = (P + MT - 1) / MT;
   const int blocks = min((ntiles + NWAVE - 1) / NWAVE, 256);
   const int arith = g_mlp_arithmetic.load(std::memory_order_relaxed);
+  const bool pos = g_dx != nullptr;   // g_dx == NULL: the position head's backward is compiled out, gw->P1..pb2 are not touched
   // S3G_MLP_BF16X3: the transposed pre-split image goes into the slot the stash reserves for it; the other modes read the fp32 image,
   // which a bf16x3 forward does not build, so they pack it into its slot (the caller's buffer: only the image regions are written)
   float* img = const_cast<float*>(stash_) + PACK_FLOATS + tpw::WORDS;
@@ -734,11 +934,15 @@ static int mlp_backward_impl(const s3g_mlp_params* w, int P, const float* featur
   if (arith == S3G_MLP_BF16X3) {
     MlpBwdArgs sb = b;
     sb.packed = img;
-    hipLaunchKernelGGL(mlp_backward_presplit_kernel, dim3(blocks), dim3(NWAVE * 64), tbw::WORDS * 4, stream, sb);
-  } else if (arith != S3G_MLP_F32)
-    hipLaunchKernelGGL(mlp_backward_kernel<true>, dim3(blocks), dim3(NWAVE * 64), MLP_LDS_FLOATS * 4, stream, b);
-  else
-    hipLaunchKernelGGL(mlp_backward_kernel<false>, dim3(blocks), dim3(NWAVE * 64), MLP_LDS_FLOATS * 4, stream, b);
+    auto k = pos ? mlp_backward_presplit_kernel : mlp_static_backward_presplit_kernel;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(NWAVE * 64), tbw::WORDS * 4, stream, sb);
+  } else if (arith != S3G_MLP_F32) {
+    auto k = pos ? mlp_backward_kernel<true> : mlp_static_backward_kernel<true>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(NWAVE * 64), MLP_LDS_FLOATS * 4, stream, b);
+  } else {
+    auto k = pos ? mlp_backward_kernel<false> : mlp_static_backward_kernel<false>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(NWAVE * 64), MLP_LDS_FLOATS * 4, stream, b);
+  }
   profile_end(S3G_PROFILE_MLP_BACKWARD, stream, (double)P, 0.0);
   S3G_HIP_CHECK(hipGetLastError());
   profile_begin(S3G_PROFILE_MLP_WGRAD, stream);

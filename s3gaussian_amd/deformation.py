@@ -3,7 +3,8 @@
 (name filter "grid") and the Adam groups of scene/gaussian_model.py:170-201 keep working.
 
 The reference's default configuration (arguments/__init__.py:202-236) runs as two fused HIP operators (HexPlane sampler +
-MFMA MLP).  Every other switch of scene/deformation.py:16-178 is honoured too -- no_dx / no_ds / no_dr / no_do / no_dshs /
+MFMA MLP), and so does its static one (arguments/static_nvs.py: no_dx=True -- the same kernels with the position head compiled
+out).  Every other switch of scene/deformation.py:16-178 is honoured too -- no_dx / no_ds / no_dr / no_do / no_dshs /
 feat_head, grid_pe (sin/cos embedding of the grid feature, :84-86), no_grid (:79-80), static_mlp and empty_voxel (the
 per-point mask of :108-114, DenseGrid of scene/grid.py:15-42), apply_rotation (:140-141) -- on the same fused sampler with
 the heads as PyTorch-ROCm library GEMMs (GPU only; nothing here runs on the CPU).
@@ -133,15 +134,16 @@ class Deformation(nn.Module):
         return self.forward_dynamic(rays_pts_emb, scales_emb, rotations_emb, opacity, shs_emb, time_feature, time_emb)
 
     def _fused_ok(self):
+        """The fused route serves the reference's default heads (dx + dshs + feat) and the static configuration (no_dx: dshs + feat)."""
         a = self.args
         plain = not (self.no_grid or self.grid_pe != 0 or getattr(a, "static_mlp", False) or getattr(a, "empty_voxel", False))
-        return (plain and self.D == 1 and self.W == 64 and self.grid.feat_dim == 128 and not a.no_dx and not a.no_dshs
+        return (plain and self.D == 1 and self.W == 64 and self.grid.feat_dim == 128 and not a.no_dshs
                 and a.no_ds and a.no_dr and a.no_do and a.feat_head)
 
     def deform_heads(self, xyz, time, uniform_time=None, reg_weights=None, need_feat=True):
         """(dx [P,3], dshs [P,16,3], feat [P,3]) only -- the part of forward_dynamic that is not a pass-through in the
         reference's default configuration.  Lets a caller that fuses `shs + dshs` downstream (pipeline.render) skip
-        materialising the [P,16,3] sum."""
+        materialising the [P,16,3] sum.  dx is None for a no_dx network (static scenes): the position head is never evaluated."""
         global infer_cache_hits
         key = None
         if INFER_CACHE and not torch.is_grad_enabled() and reg_weights is None and xyz.is_cuda:
@@ -155,7 +157,8 @@ class Deformation(nn.Module):
             if hit is not None and hit[0] == key and all(t._version == v for t, v in hit[2]):   # (a consumer edited dx in place: miss)
                 infer_cache_hits += 1
                 return hit[1]
-        if (FUSED_INFERENCE and not torch.is_grad_enabled() and not need_feat and reg_weights is None and xyz.is_cuda
+        need_dx = not self.args.no_dx
+        if (FUSED_INFERENCE and need_dx and not torch.is_grad_enabled() and not need_feat and reg_weights is None and xyz.is_cuda
                 and len(self.grid.resolutions) == 4):
             # inference render without the feature image: sampler (+) heads in one kernel, no [P,128] round trip
             dx, dshs = deform_infer(self.grid, xyz[:, :3], time[:, :1], self.feature_out, self.pos_deform, self.shs_deform,
@@ -170,7 +173,8 @@ class Deformation(nn.Module):
         else:
             feats = self.grid(xyz[:, :3], time[:, :1], uniform_time)
         # need_feat=False (honoured only when no backward follows): skip the feature head, `feat` is then None
-        dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, self.dino_head, need_feat)
+        # (a no_dx network's no_grad renders take these two kernels too: the one-kernel route has no variant without the head)
+        dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, self.dino_head, need_feat, need_dx)
         out = (dx, dshs.reshape([xyz.shape[0], 16, 3]), feat)
         if key is not None:      # (no_grad, no regulariser: what an evaluation render with the feature image asks for)
             self._keep_inference(key, out, xyz, time)
@@ -204,9 +208,10 @@ class Deformation(nn.Module):
         if self._fused_ok() and rays_pts_emb.is_cuda:
             # reference default configuration: HexPlane sampler -> one fused MFMA MLP kernel (include/s3g_mlp.h)
             feats = self.grid(rays_pts_emb[:, :3], time_emb[:, :1])
-            dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, self.dino_head)
+            dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, self.dino_head, need_dx=not a.no_dx)
             dshs = dshs.reshape([shs_emb.shape[0], 16, 3])
-            return (rays_pts_emb[:, :3] + dx, scales_emb[:, :3], rotations_emb[:, :4], opacity_emb[:, :1], shs_emb + dshs,
+            pts = rays_pts_emb[:, :3] if dx is None else rays_pts_emb[:, :3] + dx     # no_dx: scene/deformation.py:119-121
+            return (pts, scales_emb[:, :3], rotations_emb[:, :4], opacity_emb[:, :1], shs_emb + dshs,
                     dx, feat, dshs)
         # other switch combinations: fused HexPlane sampler + library GEMMs, scene/deformation.py:106-166 line by line
         hidden = self.query_time(rays_pts_emb, scales_emb, rotations_emb, time_feature, time_emb)

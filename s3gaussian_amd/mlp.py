@@ -78,9 +78,14 @@ def get_mlp_arithmetic() -> str:
     return next(k for k, x in _ARITHMETIC.items() if x == v)
 
 
+_POS = slice(2, 6)     # P1, pb1, P2, pb2: the position head's slots in _NAMES
+
+
 def _pack(tensors) -> _Params:
     p = _Params()
     for n, shape, t in zip(_NAMES, _SHAPES, tensors):
+        if t is None:      # a gradient slot the library does not touch (the position head's, when it is skipped): NULL
+            continue
         if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
             raise RuntimeError(f"deform MLP: parameter {n} must be contiguous float32 {shape}, got {tuple(t.shape)} {t.dtype}")
         setattr(p, n, t.data_ptr())
@@ -89,13 +94,16 @@ def _pack(tensors) -> _Params:
 
 class _DeformMLP(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, features, need_feat, grad_mode, *params):
+    def forward(ctx, features, need_feat, grad_mode, pos, *params):
+        # pos is None: `params` are all 16 tensors.  need_dx=False: `params` are the 12 of feature_out / shs_deform / dino_head and
+        # `pos` holds the position head's four, detached and inside a tuple -- NOT inputs of this node (the kernels skip the head but
+        # the pack kernels still copy its weights into the LDS images)
         if not features.is_cuda:
             raise RuntimeError(f"deform MLP: features must live on the GPU (got {features.device}); no CPU fallback")
         L = _bind()
         x = features.contiguous().float()
         P, dev = x.shape[0], x.device
-        dx = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        dx = torch.empty((P, 3), dtype=torch.float32, device=dev) if pos is None else None
         dshs = torch.empty((P, 48), dtype=torch.float32, device=dev)
         # needs_input_grad is True for parameters even under torch.no_grad(); the caller's grad mode decides whether a
         # backward can follow (inside Function.forward grad mode is always off)
@@ -104,12 +112,14 @@ class _DeformMLP(torch.autograd.Function):
         feat = torch.empty((P, 3), dtype=torch.float32, device=dev) if need_feat else None
         nbytes = L.s3g_deform_mlp_stash_bytes(P) if need_bwd else L.s3g_deform_mlp_pack_bytes()
         stash = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        w = _pack([p.detach() for p in params])
+        w = _pack(_all16(pos, [p.detach() for p in params]))
         with _lib.on_device(dev):
-            _lib.check(L.s3g_deform_mlp_forward(C.byref(w), P, x.data_ptr(), dx.data_ptr(), dshs.data_ptr(), feat.data_ptr() if feat is not None else None,
+            _lib.check(L.s3g_deform_mlp_forward(C.byref(w), P, x.data_ptr(), dx.data_ptr() if dx is not None else None, dshs.data_ptr(),
+                                                feat.data_ptr() if feat is not None else None,
                                                 stash.data_ptr(), int(need_bwd), _lib.stream_ptr()))
         if need_bwd:
             ctx.save_for_backward(x, stash, *params)
+            ctx.pos = pos
             ctx.set_materialize_grads(False)   # an output the loss never touched must arrive as None, not as zeros
         return dx, dshs, feat     # feat is None when the head was skipped (need_feat=False under no_grad)
 
@@ -119,7 +129,9 @@ class _DeformMLP(torch.autograd.Function):
         L = _bind()
         P, dev = x.shape[0], x.device
         z = lambda g, n: (torch.zeros((P, n), dtype=torch.float32, device=dev) if g is None else g.contiguous().float())
-        g_dx, g_dshs = z(g_dx, 3), z(g_dshs, 48)
+        pos = ctx.pos      # not None: no position head -- NULL for g_dx, no gradient slots for its parameters
+        g_dx, g_dshs = (z(g_dx, 3) if pos is None else None), z(g_dshs, 48)
+        g_dx_ptr = g_dx.data_ptr() if g_dx is not None else None
         # no gradient on the feature output (feature image not in the loss): like the reference, the dino head's parameters
         # then get grad None -- Adam skips them (no moment decay, no step count) -- and its part of the backward is skipped
         no_feat = g_feat is None
@@ -131,20 +143,26 @@ class _DeformMLP(torch.autograd.Function):
             grads.append(flat[off:off + p.numel()].view(p.shape))
             off += p.numel()
         ws = torch.empty((5, P, 64), dtype=torch.float32, device=dev)
-        w, gw = _pack([p.detach() for p in params]), _pack(grads)
+        w, gw = _pack(_all16(pos, [p.detach() for p in params])), _pack(_all16(pos and (None,) * 4, grads))
         with _lib.on_device(dev):
             if ORDERED_WGRAD_FLUSH:     # bit-reproducible weight gradients (include/s3g_mlp.h::s3g_deform_mlp_backward_ordered)
                 part = torch.empty(L.s3g_deform_mlp_wgrad_partial_bytes() // 4, dtype=torch.float32, device=dev)
-                _lib.check(L.s3g_deform_mlp_backward_ordered(C.byref(w), P, x.data_ptr(), stash.data_ptr(), g_dx.data_ptr(),
+                _lib.check(L.s3g_deform_mlp_backward_ordered(C.byref(w), P, x.data_ptr(), stash.data_ptr(), g_dx_ptr,
                                                              g_dshs.data_ptr(), None if no_feat else g_feat.data_ptr(), gx.data_ptr(),
                                                              C.byref(gw), ws.data_ptr(), part.data_ptr(), _lib.stream_ptr()))
             else:
-                _lib.check(L.s3g_deform_mlp_backward(C.byref(w), P, x.data_ptr(), stash.data_ptr(), g_dx.data_ptr(),
+                _lib.check(L.s3g_deform_mlp_backward(C.byref(w), P, x.data_ptr(), stash.data_ptr(), g_dx_ptr,
                                                      g_dshs.data_ptr(), None if no_feat else g_feat.data_ptr(), gx.data_ptr(),
                                                      C.byref(gw), ws.data_ptr(), _lib.stream_ptr()))
         if no_feat:
-            grads = [None if n.startswith(("D", "db")) else g for n, g in zip(_NAMES, grads)]
-        return (gx, None, None, *grads)
+            names = _NAMES if pos is None else _NAMES[:_POS.start] + _NAMES[_POS.stop:]
+            grads = [None if n.startswith(("D", "db")) else g for n, g in zip(names, grads)]
+        return (gx, None, None, None, *grads)
+
+
+def _all16(pos, rest):
+    """The 16 slots of _NAMES from the 12 tensors outside the position head and its 4 (`pos`); pos is None: `rest` already has all 16."""
+    return list(rest) if pos is None else list(rest[:_POS.start]) + list(pos) + list(rest[_POS.start:])
 
 
 def _head_params(feature_out, pos_deform, shs_deform, dino_head):
@@ -189,9 +207,15 @@ def deform_infer(grid, xyz, time, feature_out, pos_deform, shs_deform, dino_head
     return dx, dshs
 
 
-def deform_mlp(features, feature_out, pos_deform, shs_deform, dino_head, need_feat=True):
+def deform_mlp(features, feature_out, pos_deform, shs_deform, dino_head, need_feat=True, need_dx=True):
     """features [P,128] -> (dx [P,3], dshs [P,48], feat [P,3]) with the reference's Sequential modules as parameter
     holders (feature_out = Sequential(Linear); heads = Sequential(ReLU, Linear, ReLU, Linear); dino = Sequential(Linear,
-    ReLU, Linear, ReLU, Linear))."""
+    ReLU, Linear, ReLU, Linear)).
+    need_dx=False (static scenes, ModelHiddenParams no_dx=True): the position head is skipped in every kernel, dx is None, and
+    pos_deform's parameters are not inputs of the autograd node -- their .grad stays None, as the reference's autograd leaves it
+    when scene/deformation.py:119-121 never calls the head (Adam then neither decays their moments nor counts a step)."""
     ps = _head_params(feature_out, pos_deform, shs_deform, dino_head)
-    return _DeformMLP.apply(features, need_feat, torch.is_grad_enabled(), *ps)
+    if need_dx:
+        return _DeformMLP.apply(features, need_feat, torch.is_grad_enabled(), None, *ps)
+    pos = tuple(p.detach() for p in ps[_POS])
+    return _DeformMLP.apply(features, need_feat, torch.is_grad_enabled(), pos, *ps[:_POS.start], *ps[_POS.stop:])

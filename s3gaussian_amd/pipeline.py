@@ -462,7 +462,8 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
                                      need_feat=render_feat or torch.is_grad_enabled())
             dx, dshs, feat = heads[:3]
             plane_reg = heads[3] if regw is not None else None
-            means3D_final, scales_final, rotations_final, opacity_final = means3D + dx, scales, rotations, opacity
+            means3D_final = means3D if dx is None else means3D + dx     # dx is None: a static model (no_dx) has no position head
+            scales_final, rotations_final, opacity_final = scales, rotations, opacity
         else:
             time = torch.full((means3D.shape[0], 1), float(cam["time"]), device=dev)
             (means3D_final, scales_final, rotations_final, opacity_final, shs_final, dx, feat, dshs) = pc._deformation(
@@ -640,9 +641,11 @@ def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: 
 
 
 def _fused_route(pc: GaussianParams, pipe: SimpleNamespace) -> bool:
-    """render() takes the fused deformation route for this model: GPU tensors, the default head configuration, SH degree 3,
-    convert_SHs_python and fused_glue on."""
-    return bool(pc.get_xyz.is_cuda and pc._deformation.deformation_net._fused_ok() and pc.max_sh_degree == 3
+    """render() takes the fused deformation route for this model AND the model has a position head (a static model, no_dx=True,
+    takes the route too, but produces no dx: nothing to colour a flow with or to split dynamic from static by): GPU tensors, the
+    default head configuration, SH degree 3, convert_SHs_python and fused_glue on."""
+    net = pc._deformation.deformation_net
+    return bool(pc.get_xyz.is_cuda and net._fused_ok() and not net.args.no_dx and pc.max_sh_degree == 3
                 and getattr(pipe, "convert_SHs_python", True) and getattr(pipe, "fused_glue", True))
 
 
@@ -677,7 +680,8 @@ def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.T
     xyz = pc.get_xyz
     if not _fused_route(pc, pipe):
         raise RuntimeError("render_flows needs the fused deformation route: GPU tensors, the default head configuration "
-                           "(dx + dshs + feature head), SH degree 3, convert_SHs_python and fused_glue on")
+                           "(dx + dshs + feature head; not no_dx: a static model has no dx to colour a flow with), SH degree 3, "
+                           "convert_SHs_python and fused_glue on")
     dev = xyz.device
     times = [float(cam["time"]) for cam in cameras]
     window: Dict[float, torch.Tensor] = {}      # timestamp -> dx
@@ -765,8 +769,8 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     want_dec = any(k in ("dynamic_rgbs", "static_rgbs") for k in keys)
     if (want_flow or want_dec) and not (_fused_route(pc, pipe) and "fine" in stage):
         raise RuntimeError("evaluate_video: the decomposition and flow keys need the fused deformation route in a fine stage: GPU "
-                           "tensors, the default head configuration (dx + dshs + feature head), SH degree 3, convert_SHs_python "
-                           "and fused_glue on")
+                           "tensors, the default head configuration (dx + dshs + feature head; not no_dx: a static model has no dx), "
+                           "SH degree 3, convert_SHs_python and fused_glue on")
     if want_flow and stage != "fine":
         raise RuntimeError('evaluate_video: the flow keys are rendered by render_flows, in stage "fine"')
     dev = pc.get_xyz.device
