@@ -27,27 +27,11 @@ inline void device_setup_done(std::atomic<uint64_t>& seen) {
   if (dev < 64) seen.fetch_or(1ull << dev, std::memory_order_release);
 }
 
-constexpr int TILE_X = 16;  // reference BLOCK_X/BLOCK_Y, RAST/cuda_rasterizer/config.h:16-17
-constexpr int TILE_Y = 16;
-constexpr int TILE_PIX = TILE_X * TILE_Y;
 constexpr int WAVE = 64;
-constexpr int MAX_BIN_BLOCKS = 512;   // binning workgroups (2 per CU); each keeps a histogram of ALL tiles in LDS
-constexpr int MAX_TILES_LDS = 38000;  // (160 KiB - slack) / 4 B: largest tile grid the single-pass multisplit handles
-constexpr int NREC = 10;              // floats per instance gradient record written by the blend backward
-
-// number of binning workgroups / Gaussians per workgroup for a scene of P Gaussians
-inline int bin_blocks(int P) {
-  int nb = (P + 255) / 256;
-  return nb < 1 ? 1 : (nb > MAX_BIN_BLOCKS ? MAX_BIN_BLOCKS : nb);
-}
-inline int bin_chunk(int P) {
-  const int nb = bin_blocks(P);
-  const int per = (P + nb - 1) / nb;
-  return ((per + 63) / 64) * 64;   // whole waves; the binning workgroups step through their chunk with a guarded tail
-}
 
 // ---- error plumbing ------------------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
+void clear_error();
 #define S3G_HIP_CHECK(expr)                                                                     \
   do {                                                                                          \
     hipError_t _e = (expr);                                                                     \
@@ -81,78 +65,6 @@ struct Carver {
     return p;
   }
   size_t bytes() const { return (off + 127) & ~size_t(127); }
-};
-
-// Per-Gaussian forward state ("GeometryState").
-struct GeomState {
-  float* depths;          // [P]   view-space z
-  float2* means2D;        // [P]   pixel coordinates
-  float4* conic_opacity;  // [P]   (conic a, b, c, opacity)
-  float* cov3D;           // [P,6]
-  float* rgb;             // [P,3] SH->RGB result (only when shs given)
-  uint8_t* clamped;       // [P,3]
-  ushort4* rect;          // [P]   tile rect (min.x, min.y, max.x, max.y), zero area when culled
-  uint32_t* gauss_off;    // [P]   exclusive scan of tiles_touched: first slot of the Gaussian in slot_pos[]
-  uint32_t* tile_mask;    // [P]   rects of <= 32 tiles: bit k = tile k (row-major in the rect) survives the exact cull
-  static GeomState carve(void* p, size_t P, size_t* bytes) {
-    Carver c(p);
-    GeomState g;
-    g.depths = c.take<float>(P);
-    g.means2D = c.take<float2>(P);
-    g.conic_opacity = c.take<float4>(P);
-    g.cov3D = c.take<float>(P * 6);
-    g.rgb = c.take<float>(P * 3);
-    g.clamped = c.take<uint8_t>(P * 3);
-    g.rect = c.take<ushort4>(P);
-    g.gauss_off = c.take<uint32_t>(P);
-    g.tile_mask = c.take<uint32_t>(P);
-    if (bytes) *bytes = c.bytes();
-    return g;
-  }
-};
-
-// Per-image state ("ImageState") + the per-tile bucket bookkeeping.
-struct ImageState {
-  float* final_T;        // [H*W]
-  uint32_t* n_contrib;   // [H*W]
-  uint2* ranges;         // [tiles]  [start,end) into the sorted instance list
-  uint32_t* tile_count;  // [tiles]  instances per tile
-  uint32_t* tile_hi;     // [tiles]  ranges[t].x + deepest contributing list position (1-based) over the tile's pixels
-  uint32_t* ctrl;        // [8]      ctrl[0]=R (total instances), ctrl[1]=max instances in one tile, ctrl[2]=error flags
-  uint32_t* chunk_total; // [MAX_BIN_BLOCKS] instances emitted per binning workgroup (then its exclusive prefix)
-  uint32_t* table;       // [nb][tiles] per-workgroup, per-tile instance counts (then exclusive prefix over workgroups)
-  static ImageState carve(void* p, size_t N, size_t tiles, size_t nb, size_t* bytes) {
-    Carver c(p);
-    ImageState s;
-    s.final_T = c.take<float>(N);
-    s.n_contrib = c.take<uint32_t>(N);
-    s.ranges = c.take<uint2>(tiles);
-    s.tile_count = c.take<uint32_t>(tiles);
-    s.tile_hi = c.take<uint32_t>(tiles);
-    s.ctrl = c.take<uint32_t>(8);
-    s.chunk_total = c.take<uint32_t>(MAX_BIN_BLOCKS);
-    s.table = c.take<uint32_t>(nb * tiles);
-    if (bytes) *bytes = c.bytes();
-    return s;
-  }
-};
-
-// Per-instance state ("BinningState").
-struct BinningState {
-  uint64_t* keys;        // [R]  (depth bits << 32 | gaussian index), sorted ascending inside each tile range
-  uint32_t* point_list;  // [R]  gaussian index, tile-major, front-to-back
-  uint32_t* slot_pos;    // [S]  slot_pos[gauss_off[g] + k] = position in point_list of g's k-th tile (row-major in its rect),
-                         //      0xffffffff if that tile was culled.  S = sum of rect areas >= R; LAST in the arena so that
-                         //      code which only knows R (backward, reuse) still finds it.
-  static BinningState carve(void* p, size_t R, size_t S, size_t* bytes) {
-    Carver c(p);
-    BinningState b;
-    b.keys = c.take<uint64_t>(R);
-    b.point_list = c.take<uint32_t>(R);
-    b.slot_pos = c.take<uint32_t>(S);
-    if (bytes) *bytes = c.bytes();
-    return b;
-  }
 };
 
 // ---- small device helpers -------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 // writes it (glm 0.9.9.9 mat3 products expanded in glm's own summation order, type_mat3x3.inl:486-518), so the
 // per-Gaussian integer outputs (radii, tile rectangles, instance counts) are bit-identical to the fp32 oracle.
 #pragma once
-#include "common.hpp"
+#include "raster_dev.hpp"
 
 namespace s3g {
 
@@ -92,6 +92,19 @@ struct StagedGaussian {  // 48 B, three ds_read_b128
   float4 b;              // qc, opacity, depth, r
   float4 c;              // g, b, conic.x, conic.y       (un-scaled conic only used by the backward epilogue)
 };
+
+// One entry of a tile's list as the forward blends stage it (the backward stages c.z = c.w = 0 and keeps its own lines).
+__device__ __forceinline__ StagedGaussian stage_gaussian(uint32_t id, const float2* __restrict__ means2D,
+                                                         const float4* __restrict__ conic_opacity,
+                                                         const float* __restrict__ depths, const float* __restrict__ colors) {
+  const float2 m = means2D[id];
+  const float4 co = conic_opacity[id];
+  StagedGaussian s;
+  s.a = make_float4(m.x, m.y, -0.5f * LOG2E * co.x, -LOG2E * co.y);
+  s.b = make_float4(-0.5f * LOG2E * co.z, co.w, depths[id], colors[3 * (size_t)id]);
+  s.c = make_float4(colors[3 * (size_t)id + 1], colors[3 * (size_t)id + 2], co.x, co.y);
+  return s;
+}
 
 // Can this Gaussian put alpha >= 1/255 on ANY pixel of tile (tx, ty)?  The reference bins a Gaussian into every tile of
 // the bounding square of its 3-sigma radius (auxiliary.h:46-56 getRect); an elongated Gaussian never touches most of them

@@ -19,6 +19,7 @@
 //   5. geometry_backward_kernel gathers each Gaussian's records through slot_pos[] (the instance -> position map
 //      the forward's sort emitted), applies the factored-out coefficients and runs the per-Gaussian chain.
 #include "geom_math.hpp"
+#include "raster_dev.hpp"
 
 namespace s3g {
 
@@ -646,11 +647,12 @@ static int raster_backward_impl(const char* who, const s3g_raster_inputs* in, co
     set_error("%s: NULL array argument", who);
     return S3G_ERR_INVALID_ARG;
   }
-  const int gx = (W + TILE_X - 1) / TILE_X, gy = (H + TILE_Y - 1) / TILE_Y, tiles = gx * gy;
   const bool debug = in->debug != 0;
-  GeomState g = GeomState::carve(const_cast<void*>(geometry_arena), P, nullptr);
-  ImageState im = ImageState::carve(const_cast<void*>(image_arena), (size_t)W * H, tiles, bin_blocks(P), nullptr);
-  BinningState b = BinningState::carve(const_cast<void*>(binning_arena), (size_t)(R > 0 ? R : 0), 0, nullptr);
+  const Arenas a = reopen_arenas(in, R, geometry_arena, binning_arena, image_arena);
+  const int gx = a.gx, tiles = a.tiles;
+  const GeomState& g = a.g;
+  const ImageState& im = a.im;
+  const BinningState& b = a.b;
   float* records = reinterpret_cast<float*>(workspace);
 
   const float* color_ptr = in->colors_precomp ? in->colors_precomp : g.rgb;

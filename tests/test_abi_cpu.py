@@ -236,3 +236,25 @@ def test_hexplane_workspace_layout_is_what_the_single_file_library_carved():
                 assert got == bwd, (det, ut, have_features, got)
     finally:
         L.s3g_hexplane_set_deterministic(prev)
+
+
+def test_raster_arena_layout_is_what_the_single_file_library_carved():
+    """GeomState / BinningState / ImageState::carve (csrc/raster_dev.hpp) are host code: no kernel comparison covers them.  The three
+    byte counts s3g_raster_arena_bytes reports (it launches nothing) are compared with literals recorded from the library of commit
+    72424ac, the last one with the whole forward in one raster_forward.hip.  P = 131 071 and 131 073 straddle bin_blocks saturating
+    at 512 workgroups (the image arena holds their [workgroup][tile] table); the last case has counts beyond 32 bits of bytes."""
+    import ctypes as C
+    from s3gaussian_amd import _lib
+    L = _lib.lib()
+    # (P, W, H, capacity_instances, capacity_slots) -> geometry, binning, image bytes       recorded from 72424ac
+    recorded = {
+        (0, 16, 16, 1, 1): (0, 384, 4736),
+        (1, 17, 1, 1, 1): (1152, 384, 2944),
+        (131071, 1600, 1066, 1 << 20, 1 << 21): (10878976, 20971520, 27475968),
+        (131073, 1600, 1066, 1 << 20, 1 << 21): (10880128, 20971520, 27475968),
+        (1200000, 7680, 4320, 0x7fffffff, 0xffffffff): (99600000, 42949672960, 532917376),
+    }
+    for case, want in recorded.items():
+        n = [C.c_size_t(), C.c_size_t(), C.c_size_t()]
+        assert L.s3g_raster_arena_bytes(*case, C.byref(n[0]), C.byref(n[1]), C.byref(n[2])) == 0, case
+        assert tuple(x.value for x in n) == want, (case, tuple(x.value for x in n))

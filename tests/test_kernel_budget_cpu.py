@@ -75,7 +75,7 @@ def test_round4_latency_fixes_keep_their_occupancy(built):
     for needle in ("geometry_backward_kernelILi0E", "geometry_backward_kernelILi3E"):
         vgpr, scratch = _one(bwd, needle)          # three tiles of a rect in flight: still five waves per SIMD (four tiles: 105)
         assert vgpr <= 96 and scratch == 0, (needle, vgpr, scratch)
-    fwd = _resources("raster_forward.o")
+    fwd = _resources("raster_bin.o")
     for needle in ("bin_kernelILb0E", "bin_kernelILb1E"):
         vgpr, scratch = _one(fwd, needle)          # 512 threads x 2 workgroups per CU = four waves per SIMD
         assert vgpr <= 128 and scratch == 0, (needle, vgpr, scratch)

@@ -99,7 +99,7 @@ def _long_lists():
 
 def _bucket_lists(P, seed):
     """Round 6: lists of (1024, 4096] keys take the bucket pass of the per-tile sort in a launch of their own, lists of (4096, 7424]
-    keys in the long-list launch (csrc/raster_forward.hip::bucket_sort_lds); two tiles share P Gaussians here."""
+    keys in the long-list launch (csrc/raster_sort.hip::bucket_sort_lds); two tiles share P Gaussians here."""
     s = tiny_scene(P=P, W=32, H=16, seed=seed, scale=0.02, spread=0.25)
     s["opacities"] = s["opacities"] * 0.05
     return s

@@ -37,7 +37,7 @@ def test_glue_forward_staging_walk_visits_every_coefficient_once(nrows):
 
 @pytest.mark.parametrize("tiles", [1, 1023, 1024, 1025, 6700, 38000, 129600])
 def test_scan_tiles_partition_covers_every_tile_once(tiles):
-    """csrc/raster_forward.hip::scan_tiles_kernel: thread t owns tiles [t * per, min(tiles, (t + 1) * per)), per = ceil(tiles / 1024);
+    """csrc/raster_bin.hip::scan_tiles_kernel: thread t owns tiles [t * per, min(tiles, (t + 1) * per)), per = ceil(tiles / 1024);
     ranges = exclusive scan in tile order."""
     g = np.random.default_rng(tiles)
     cnt = g.integers(0, 500, size=tiles).astype(np.uint32)

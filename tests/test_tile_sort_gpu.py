@@ -1,4 +1,4 @@
-"""The per-tile sort at the boundaries of its code paths (csrc/raster_forward.hip::sort_tiles_kernel, round 6): ONE 16x16 tile holding
+"""The per-tile sort at the boundaries of its code paths (csrc/raster_sort.hip::sort_tiles_kernel, round 6): ONE 16x16 tile holding
 exactly n instances, n on both sides of every switch -- <= 256 keys ranked by counting, <= 512 on the bitonic network, (512, 4096] bucket
 pass in the medium launch, (4096, 7616] bucket pass in the long-list launch, <= 16384 network in LDS, longer lists network in global
 memory -- and with depth ties of every size (the index decides; a tie of thousands of instances is ONE bucket).  The expected list is

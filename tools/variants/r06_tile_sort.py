@@ -3,8 +3,8 @@
     python tools/mkvariants.py tools/variants/r06_tile_sort.py; bash tools/ab_kstats_heavy.sh "tree ts_min1024 ts_min256 ts_bins4096 ts_bins1024" """
 _C = "constexpr int SORT_BIN_BITS = 11;\nconstexpr uint32_t SORT_BINS = 1u << SORT_BIN_BITS, BUCKET_MIN = 512,"
 VARIANTS = {
-    "ts_min1024": ("raster_forward.hip", [(_C, _C.replace("BUCKET_MIN = 512", "BUCKET_MIN = 1024"))]),
-    "ts_min256": ("raster_forward.hip", [(_C, _C.replace("BUCKET_MIN = 512", "BUCKET_MIN = 256"))]),
-    "ts_bins4096": ("raster_forward.hip", [(_C, _C.replace("SORT_BIN_BITS = 11", "SORT_BIN_BITS = 12"))]),
-    "ts_bins1024": ("raster_forward.hip", [(_C, _C.replace("SORT_BIN_BITS = 11", "SORT_BIN_BITS = 10"))]),
+    "ts_min1024": ("raster_sort.hip", [(_C, _C.replace("BUCKET_MIN = 512", "BUCKET_MIN = 1024"))]),
+    "ts_min256": ("raster_sort.hip", [(_C, _C.replace("BUCKET_MIN = 512", "BUCKET_MIN = 256"))]),
+    "ts_bins4096": ("raster_sort.hip", [(_C, _C.replace("SORT_BIN_BITS = 11", "SORT_BIN_BITS = 12"))]),
+    "ts_bins1024": ("raster_sort.hip", [(_C, _C.replace("SORT_BIN_BITS = 11", "SORT_BIN_BITS = 10"))]),
 }
