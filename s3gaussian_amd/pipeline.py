@@ -235,15 +235,32 @@ class GaussianParams(nn.Module):
 
     @torch.no_grad()
     def save_ply(self, path):
-        """scene/gaussian_model.py:258-275: same attribute order and layout (SH coefficients channel-major)."""
+        """scene/gaussian_model.py:258-275: same attribute order and layout (SH coefficients channel-major).  On the GPU the table is
+        built by one launch (split.pack_ply_rows) and crosses to the host in one copy; the file is the same, byte for byte."""
         import numpy as np
         from .plyio import write_vertices
+        if self._xyz.is_cuda:
+            from . import split
+            write_vertices(path, self.construct_list_of_attributes(), split.model_rows(self).cpu().numpy())
+            return
         n = lambda t_: t_.detach().cpu().numpy()
         xyz = n(self._xyz)
         cols = [xyz, np.zeros_like(xyz), n(self._features_dc.transpose(1, 2).flatten(start_dim=1).contiguous()),
                 n(self._features_rest.transpose(1, 2).flatten(start_dim=1).contiguous()), n(self._opacity), n(self._scaling),
                 n(self._rotation)]
         write_vertices(path, self.construct_list_of_attributes(), np.concatenate(cols, axis=1))
+
+    @torch.no_grad()
+    def save_ply_split(self, dynamic_pcd_path, static_pcd_path, dx_list, visibility_filter=None, index=24):
+        """scene/gaussian_model.py:277-348: the Gaussians whose displacement dx = dx_list[index] exceeds the mean, max|dx_i| >
+        mean_j max|dx_j|, go to `dynamic_pcd_path`, the others to `static_pcd_path`, both at their deformed positions xyz + dx and in
+        source order.  The reference hard-codes entry 24 (a shorter list raises the same IndexError) and never looks at
+        `visibility_filter`; neither does this.
+        One deliberate difference: the reference rebinds `self._xyz = self._xyz + dx` on the way, which leaves a non-Parameter tensor
+        behind the optimizer's back; here the model is left untouched.  The files are the same.
+        -> {"n_dynamic", "n_static", "thre"} (the reference returns None)."""
+        from . import split
+        return split.export_split(self, dx_list[index], dynamic_pcd_path, static_pcd_path)
 
     @torch.no_grad()
     def load_ply(self, path, device=None):
@@ -723,6 +740,35 @@ def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.T
         if i + 1 == len(cameras) or times[i + 1] != times[i]:
             entries[times[i]] = None             # the timestamp's frames are done: only its dx is still needed, not its dshs
     return result
+
+
+def dynamic_point_count(dx: torch.Tensor) -> torch.Tensor:
+    """The "dynamic point" number of the reference's training log (train.py:445-452): #{i : max|dx_i| > mean_j max|dx_j|}, as a 0-dim
+    int32 tensor on dx's device.  Nothing here waits for the device (no boolean index, no .item()): the caller reads the number when
+    it logs, which keeps run_training_steps host-asynchronous."""
+    from . import split
+    return split.motion_classify(dx)[2]
+
+
+@torch.no_grad()
+def save_split_point_clouds(pc: GaussianParams, time: float, dynamic_pcd_path: str, static_pcd_path: str, stage: str = "fine") -> Dict:
+    """The export of utils/video_utils.py:243-250 (`save_seperate_pcd`) for one timestamp: the deformation is evaluated once at
+    `time` through net.deform_heads -- a frame of that timestamp rendered before or after shares the evaluation through the inference
+    cache -- and the model is split by that dx exactly as GaussianParams.save_ply_split splits it.
+    A static model (no_dx) is refused: it has no dx to tell moving from static by; so is any stage without a deformation.
+    -> {"n_dynamic", "n_static", "thre"}."""
+    from . import split
+    net = pc._deformation.deformation_net
+    if net.args.no_dx:
+        raise RuntimeError("save_split_point_clouds: the model was built with no_dx (a static scene): there is no dx to split "
+                           "dynamic from static points by")
+    if "fine" not in stage:
+        raise RuntimeError(f"save_split_point_clouds: stage {stage!r} has no deformation; only the fine stage has a dx")
+    xyz = pc.get_xyz
+    if not (xyz.is_cuda and net._fused_ok()):
+        raise RuntimeError("save_split_point_clouds needs GPU tensors and the default head configuration (dx + dshs + feature head)")
+    dx = net.deform_heads(xyz, _uniform_time(float(time), xyz.device), uniform_time=True, reg_weights=None, need_feat=False)[0]
+    return split.export_split(pc, dx, dynamic_pcd_path, static_pcd_path)
 
 
 VIDEO_KEYS = ("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs", "forward_flows", "backward_flows")
