@@ -69,7 +69,7 @@ class Adam(torch.optim.Adam):
         if p.dtype != torch.float32 or not _dense(p):
             raise RuntimeError("s3gaussian_amd.optim.Adam handles dense float32 parameters only")
         e = _Entry()
-        e.p, e.stride, e.device = p, p.stride(), p.device
+        e.p, e.shape, e.stride, e.device = p, p.shape, p.stride(), p.device
         e.contig = p.is_contiguous()
         e.rec = _AdamTensor(p.data_ptr(), None, None, None, p.numel(), 0.0, 0.0, 0.0, 1.0)
         e.p_ptr, e.m, e.v = p.data_ptr(), None, None
@@ -80,7 +80,10 @@ class Adam(torch.optim.Adam):
     def step(self, closure=None):
         """Host side: ~4 us per parameter before the launch (the launch records are kept from step to step; only the gradient pointer and
         the step-dependent scalars are written) -- on the zero-edit route the GPU sits idle behind train.py's `loss.item()` until this
-        launch is out, so every microsecond in front of it is a microsecond of the iteration (profiles/r05_patched_iteration_trace.txt)."""
+        launch is out, so every microsecond in front of it is a microsecond of the iteration (profiles/r05_patched_iteration_trace.txt).
+        A kept record is valid for the same Parameter object with the same address, shape and stride: the last two cost one attribute
+        read, one call and two tuple comparisons per parameter (~0.3 us), and without them `p.data = p.data[mask]` landing on the old
+        address would step over the old extent (tests/test_optim_trajectory_gpu.py::test_p_data_repointed_at_the_same_address)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -106,7 +109,9 @@ class Adam(torch.optim.Adam):
                 if g is None:
                     continue
                 e = entries.get(id(p))
-                if e is None or e.p is not p or e.p_ptr != p.data_ptr():
+                # the record holds numel and the layout: `p.data` re-pointed to another size at the SAME address (a view into a
+                # caller's flat buffer, or the allocator handing the freed block straight back) must not step over the old extent
+                if e is None or e.p is not p or e.p_ptr != p.data_ptr() or e.shape != p.shape or e.stride != p.stride():
                     e = entries[id(p)] = self._entry(group, p)
                     stale = True
                 if g.layout is not strided:
@@ -125,6 +130,9 @@ class Adam(torch.optim.Adam):
                 m, v = st["exp_avg"], st["exp_avg_sq"]
                 if m is not e.m or v is not e.v:          # first step, or densification / load_state_dict replaced the moments
                     for name in ("exp_avg", "exp_avg_sq"):
+                        if st[name].numel() != e.rec.numel:   # the kernel would run past its end (or leave its end behind)
+                            raise RuntimeError(f"s3gaussian_amd.optim.Adam: state['{name}'] has {st[name].numel()} elements, "
+                                               f"its parameter {e.rec.numel}")
                         if st[name].stride() != e.stride:     # ... possibly with another layout
                             st[name] = torch.empty_like(p, memory_format=torch.preserve_format).copy_(st[name])
                     m, v = e.m, e.v = st["exp_avg"], st["exp_avg_sq"]
@@ -191,7 +199,7 @@ class Adam(torch.optim.Adam):
 
 
 class _Entry:
-    __slots__ = ("p", "stride", "device", "rec", "p_ptr", "m", "v", "contig", "st", "state_obj", "step_t", "step_val", "step_ver")
+    __slots__ = ("p", "shape", "stride", "device", "rec", "p_ptr", "m", "v", "contig", "st", "state_obj", "step_t", "step_val", "step_ver")
 
 
 @torch.no_grad()
