@@ -1,14 +1,19 @@
 /*
- * s3g_loss.h -- C ABI of the fused SSIM loss kernels (libs3g.so).
+ * s3g_loss.h -- C ABI of the loss kernels (libs3g.so): SSIM, the per-pixel photometric terms, the HexPlane regulariser.
  *
  *   s3g_ssim_forward / s3g_ssim_backward  <- ssim() / _ssim()  /root/reference/utils/loss_utils.py:66-96
  *       (create_window :60-64: 11x11 window = outer product of a sigma=1.5 Gaussian; five grouped F.conv2d with
  *        zero padding 5; C1 = 0.01^2, C2 = 0.03^2; mean over all channels and pixels) and its autograd.
+ *   s3g_photometric_forward / s3g_photometric_backward: the same two passes with the per-pixel terms of the training
+ *       loss (s3g_pixel_losses_* below) folded in, so the image-space loss stage of a step is two launches + the combine.
  *
- * The window is separable, so each statistic is one horizontal + one vertical 11-tap pass through LDS; forward keeps
- * three per-pixel partial-derivative maps so backward is three more separable passes instead of replaying five
- * convolutions and ~25 elementwise kernels.  Only img1 (the rendered image) receives a gradient, like the reference's
- * call site train.py:416-418 (the ground truth needs none).
+ * The window is separable.  A wave owns a strip of 64 columns x 21 rows of one channel and walks down its 31 input rows:
+ * each row passes through a wave-private LDS row buffer for the horizontal 11-tap sums (no workgroup barrier), a register
+ * ring of the last 11 rows of sums gives the vertical sums.  Forward keeps three per-pixel partial-derivative maps so
+ * backward is three more separable passes instead of replaying five convolutions and ~25 elementwise kernels; two passes
+ * remain because the gradient convolves those maps, which exist only once the forward convolution has finished.  Only
+ * img1 (the rendered image) receives a gradient, like the reference's call site train.py:416-418 (the ground truth
+ * needs none).
  */
 #ifndef S3G_LOSS_H
 #define S3G_LOSS_H
@@ -96,6 +101,31 @@ int s3g_pixel_losses_backward(int H, int W, const float* image, const float* gt_
                               const float* gt_depth, const float* feat, const float* gt_feat, float max_depth,
                               const double* totals, const float* g, float w_l1, float w_depth, float w_feat,
                               float* g_image, int accumulate_image, float* g_depth, float* g_feat, void* stream);
+
+/*
+ *   s3g_photometric_*  <- s3g_ssim_* and s3g_pixel_losses_* of one view in one launch each way (w_ssim != 0).
+ *
+ * Forward: image, gt_image [3,H,W]; (depth, gt_depth) [H,W] and (feat, gt_feat) [3,H,W] may each be NULL as a pair.
+ * Writes the three maps dm_dmu1, dm_dsigma1_sq, dm_dsigma12 ([3,H,W] each, every element) and ADDS into sums, the five
+ * slotted accumulators of s3g_pixel_losses_forward (5 * S3G_SUM_DOUBLES doubles, caller zeroes): [0] SSIM map, [1]
+ * sum|image-gt|, [2] masked squared depth error, [3] mask count, [4] sum (feat-gt)^2; [2] [3] are touched only with a depth
+ * pair, [4] only with a feature pair.  s3g_pixel_losses_combine then produces totals and the loss.  The per-pixel values are
+ * those of the separate entry points; the partial sums are grouped per wave, so a total may differ in its last bits.
+ */
+int s3g_photometric_forward(int H, int W, const float* image, const float* gt_image, const float* depth,
+                            const float* gt_depth, const float* feat, const float* gt_feat, float max_depth, double* sums,
+                            float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, void* stream);
+
+/* Backward of  w_l1*L1 + w_depth*depth_l2 + w_ssim*(1 - ssim) + w_feat*feat_l2  times the upstream device scalar *g.
+ * g_image[3,H,W] (required) = SSIM term + L1 term, in that order: the SSIM term is s3g_ssim_backward's with
+ * dL_dmean = *g * (-w_ssim), formed in the kernel.  g_depth[H,W] and g_feat[3,H,W] are as s3g_pixel_losses_backward writes
+ * them and may each be NULL (their inputs may then be NULL too).  Every element of every non-NULL output is written.
+ * The maps are the forward's; totals: the five doubles s3g_pixel_losses_combine wrote (only [3] is read, with g_depth). */
+int s3g_photometric_backward(int H, int W, const float* image, const float* gt_image, const float* depth,
+                             const float* gt_depth, const float* feat, const float* gt_feat, float max_depth,
+                             const float* dm_dmu1, const float* dm_dsigma1_sq, const float* dm_dsigma12,
+                             const double* totals, const float* g, float w_ssim, float w_l1, float w_depth, float w_feat,
+                             float* g_image, float* g_depth, float* g_feat, void* stream);
 
 #ifdef __cplusplus
 }

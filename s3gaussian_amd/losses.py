@@ -11,6 +11,9 @@ from . import _lib
 
 _bound = False
 SUM_DOUBLES = 64 * 16   # S3G_SUM_DOUBLES (include/s3g_loss.h): one slotted accumulator
+# allocators of the kernels' outputs: every element is written, which the tests check by poisoning what these return
+_new_grad = torch.empty_like
+_new_maps = torch.empty
 
 
 def _bind():
@@ -29,6 +32,11 @@ def _bind():
         L.s3g_pixel_losses_backward.restype = C.c_int
         L.s3g_pixel_losses_backward.argtypes = ([C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, C.c_float,
                                                  C.c_float, C.c_float, vp, C.c_int, vp, vp, vp])
+        L.s3g_photometric_forward.restype = C.c_int
+        L.s3g_photometric_forward.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]
+        L.s3g_photometric_backward.restype = C.c_int
+        L.s3g_photometric_backward.argtypes = ([C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp,
+                                                C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp])
         _bound = True
     return L
 
@@ -45,7 +53,7 @@ class _SSIM(torch.autograd.Function):
             raise RuntimeError("ssim: shape mismatch")
         Cn, H, W = a.shape
         total = torch.zeros(SUM_DOUBLES, dtype=torch.float64, device=a.device)
-        maps = torch.empty((3, Cn, H, W), dtype=torch.float32, device=a.device)
+        maps = _new_maps((3, Cn, H, W), dtype=torch.float32, device=a.device)
         with _lib.on_device(a.device):
             _lib.check(L.s3g_ssim_forward(Cn, H, W, a.data_ptr(), b.data_ptr(), total.data_ptr(), maps[0].data_ptr(),
                                           maps[1].data_ptr(), maps[2].data_ptr(), _lib.stream_ptr()))
@@ -59,7 +67,7 @@ class _SSIM(torch.autograd.Function):
         L = _bind()
         Cn, H, W = a.shape
         g = g.detach().reshape(1).contiguous().float()
-        out = torch.empty_like(a)
+        out = _new_grad(a)
         with _lib.on_device(a.device):
             _lib.check(L.s3g_ssim_backward(Cn, H, W, a.data_ptr(), b.data_ptr(), maps[0].data_ptr(), maps[1].data_ptr(),
                                            maps[2].data_ptr(), g.data_ptr(), out.data_ptr(),
@@ -74,8 +82,9 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11, size_ave
 
 
 class _PhotometricLoss(torch.autograd.Function):
-    """l1(image, gt) + w_depth * depth_l2 + w_ssim * (1 - ssim(image, gt)) + w_feat * l2(feat, gt_feat) as three kernels
-    forward and two backward (include/s3g_loss.h)."""
+    """l1(image, gt) + w_depth * depth_l2 + w_ssim * (1 - ssim(image, gt)) + w_feat * l2(feat, gt_feat): with an SSIM term one
+    fused launch plus the 64-lane combine forward and one launch backward (include/s3g_loss.h::s3g_photometric_*); without it
+    the pixel-loss entry points."""
 
     @staticmethod
     def forward(ctx, image, gt_image, depth, gt_depth, feat, gt_feat, w_ssim, w_depth, w_feat, max_depth):
@@ -96,15 +105,17 @@ class _PhotometricLoss(torch.autograd.Function):
                 raise RuntimeError("photometric_loss: depth must have H*W and feat 3*H*W elements, like their targets")
         sums = torch.zeros(5 * SUM_DOUBLES + 5, dtype=torch.float64, device=dev)   # 5 accumulators + their 5 totals
         totals = sums[5 * SUM_DOUBLES:]
-        maps = torch.empty((3, 3, H, W), dtype=torch.float32, device=dev) if w_ssim != 0.0 else None
+        maps = _new_maps((3, 3, H, W), dtype=torch.float32, device=dev) if w_ssim != 0.0 else None
         loss = torch.empty((), dtype=torch.float32, device=dev)
         p = lambda t: None if t is None else t.data_ptr()
         with _lib.on_device(dev):
             st = _lib.stream_ptr()
             if maps is not None:
-                _lib.check(L.s3g_ssim_forward(3, H, W, p(img), p(gt), p(sums), p(maps[0]), p(maps[1]), p(maps[2]), st))
-            _lib.check(L.s3g_pixel_losses_forward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), float(max_depth),
-                                                  p(sums), st))
+                _lib.check(L.s3g_photometric_forward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), float(max_depth),
+                                                     p(sums), p(maps[0]), p(maps[1]), p(maps[2]), st))
+            else:
+                _lib.check(L.s3g_pixel_losses_forward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), float(max_depth),
+                                                      p(sums), st))
             _lib.check(L.s3g_pixel_losses_combine(H, W, p(sums), p(totals), 1.0, w_depth if dep is not None else 0.0, w_ssim,
                                                   w_feat if ft is not None else 0.0, p(loss), st))
         ctx.save_for_backward(img, gt, *(t for t in (dep, gdep, ft, gft, maps) if t is not None), totals)
@@ -132,17 +143,19 @@ class _PhotometricLoss(torch.autograd.Function):
         L = _bind()
         dev = img.device
         g = g.detach().reshape(1).contiguous().float()
-        g_img = torch.empty_like(img)
-        g_dep = torch.empty_like(dep) if has_d else None
-        g_ft = torch.empty_like(ft) if has_f else None
+        g_img = _new_grad(img)
+        g_dep = _new_grad(dep) if has_d else None
+        g_ft = _new_grad(ft) if has_f else None
         p = lambda t: None if t is None else t.data_ptr()
         with _lib.on_device(dev):
             st = _lib.stream_ptr()
             if has_s:
-                gs = g * (-w_ssim)
-                _lib.check(L.s3g_ssim_backward(3, H, W, p(img), p(gt), p(maps[0]), p(maps[1]), p(maps[2]), p(gs), p(g_img), st))
-            _lib.check(L.s3g_pixel_losses_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(sums), p(g),
-                                                   1.0, w_depth, w_feat, p(g_img), int(has_s), p(g_dep), p(g_ft), st))
+                _lib.check(L.s3g_photometric_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(maps[0]),
+                                                      p(maps[1]), p(maps[2]), p(sums), p(g), w_ssim, 1.0, w_depth, w_feat,
+                                                      p(g_img), p(g_dep), p(g_ft), st))
+            else:
+                _lib.check(L.s3g_pixel_losses_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(sums),
+                                                       p(g), 1.0, w_depth, w_feat, p(g_img), 0, p(g_dep), p(g_ft), st))
         return (g_img.view(ishape), None, g_dep.view(dshape) if has_d else None, None,
                 g_ft.view(fshape) if has_f else None, None, None, None, None, None)
 
@@ -210,9 +223,9 @@ class _PixelTerms(torch.autograd.Function):
         L = _bind()
         g = g.detach().reshape(1).contiguous().float()
         need = ctx.needs_input_grad
-        g_img = torch.empty_like(img) if (has_i and need[0]) else None
-        g_dep = torch.empty_like(dep) if (has_d and need[2]) else None
-        g_ft = torch.empty_like(ft) if (has_f and need[4]) else None
+        g_img = _new_grad(img) if (has_i and need[0]) else None
+        g_dep = _new_grad(dep) if (has_d and need[2]) else None
+        g_ft = _new_grad(ft) if (has_f and need[4]) else None
         p = lambda t: None if t is None else t.data_ptr()
         with _lib.on_device(totals.device):
             _lib.check(L.s3g_pixel_losses_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(totals), p(g),

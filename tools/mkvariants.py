@@ -19,6 +19,7 @@ SRC = os.path.join(ROOT, "s3gaussian_amd", "csrc")
 LIB = os.path.join(ROOT, "s3gaussian_amd", "lib")
 OUT = os.path.join(LIB, "variants")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics"]
+FILE_FLAGS = {"ssim.hip": ["-fno-slp-vectorize"]}      # the Makefile's per-file additions
 
 
 def build(name, hip, edits):
@@ -31,7 +32,7 @@ def build(name, hip, edits):
     obj = os.path.join(OUT, f"{name}.o")
     try:
         open(tmp_src, "w").write(src)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", *FLAGS, "-c", tmp_src, "-o", obj])
+        subprocess.check_call(["/opt/rocm/bin/hipcc", *FLAGS, *FILE_FLAGS.get(hip, []), "-c", tmp_src, "-o", obj])
     finally:
         if os.path.exists(tmp_src):
             os.remove(tmp_src)
