@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import lpips as _lpips
 from . import metrics as _metrics
 from .deformation import deform_network
 from .glue import activations_and_colors
@@ -634,27 +635,46 @@ def psnr(img1, img2):
 
 
 def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: torch.Tensor, masks=None, stage="fine",
-             return_decomposition=False) -> Dict:
+             return_decomposition=False, lpips=None) -> Dict:
     """The metric part of the reference's evaluation loop (utils/video_utils.py:169-241, 301-307): every camera is rendered under
     no_grad, frame i's {psnr, ssim, masked_psnr, masked_ssim, masked_pixels} goes into row i of one [N,5] device tensor
     (metrics.image_metrics), and that tensor is read back ONCE after the last frame.  masks: None, or one entry per camera (None
     for a camera without a dynamic mask).  The four scalars are the reference's `non_zero_mean`: the mean over the frames that
     contributed -- for the masked pair the frames with at least one masked pixel -- and -1 when none did.  "per_frame" is the
-    [N,5] table on the host.  LPIPS is not computed."""
+    [N,5] table on the host.
+    lpips: None, or an s3gaussian_amd.lpips.LPIPS model (the caller's weights): frame i's {total, tap0..tap4} goes into row i of an
+    [N,6] device tensor that is read back with the metrics table; the result gains "lpips" (non_zero_mean of the totals,
+    utils/video_utils.py:210, 305) and "lpips_per_frame" ([N,6] float64 on the host).  Without a model nothing changes."""
     n = len(cameras)
     if len(gt_images) != n or (masks is not None and len(masks) != n):
         raise RuntimeError("evaluate: one ground-truth image (and one mask entry) per camera")
     table = torch.empty((n, _metrics.RECORD), dtype=torch.float64, device=pc.get_xyz.device)
+    lpips_table = _lpips_table(lpips, n, pc.get_xyz.device)
     with torch.no_grad():
         for i, cam in enumerate(cameras):
             pkg = render(cam, pc, pipe, bg, stage=stage, return_decomposition=return_decomposition)
             _metrics.image_metrics(pkg["render"], gt_images[i], None if masks is None else masks[i], out=table[i])
+            if lpips is not None:
+                _lpips.lpips(lpips, pkg["render"], gt_images[i], out=lpips_table[i])
     per_frame = table.cpu()
     non_zero_mean = lambda x: float(x.sum() / len(x)) if len(x) > 0 else -1      # video_utils.py:44-46
     contributed = per_frame[:, _metrics.MASKED_PIXELS] > 0
-    return {"psnr": non_zero_mean(per_frame[:, _metrics.PSNR]), "ssim": non_zero_mean(per_frame[:, _metrics.SSIM]),
-            "masked_psnr": non_zero_mean(per_frame[contributed, _metrics.MASKED_PSNR]),
-            "masked_ssim": non_zero_mean(per_frame[contributed, _metrics.MASKED_SSIM]), "per_frame": per_frame}
+    result = {"psnr": non_zero_mean(per_frame[:, _metrics.PSNR]), "ssim": non_zero_mean(per_frame[:, _metrics.SSIM]),
+              "masked_psnr": non_zero_mean(per_frame[contributed, _metrics.MASKED_PSNR]),
+              "masked_ssim": non_zero_mean(per_frame[contributed, _metrics.MASKED_SSIM]), "per_frame": per_frame}
+    if lpips is not None:
+        lpips_per_frame = lpips_table.cpu()
+        result.update({"lpips": non_zero_mean(lpips_per_frame[:, _lpips.TOTAL]), "lpips_per_frame": lpips_per_frame})
+    return result
+
+
+def _lpips_table(model, n: int, device):
+    """The [N,6] device table evaluate() and evaluate_video() fill with one lpips call per frame; None without a model."""
+    if model is None:
+        return None
+    if not isinstance(model, _lpips.LPIPS):
+        raise TypeError("evaluate: lpips must be None or an s3gaussian_amd.lpips.LPIPS model")
+    return torch.empty((n, _lpips.RECORD), dtype=torch.float64, device=device)
 
 
 def _fused_route(pc: GaussianParams, pipe: SimpleNamespace) -> bool:
@@ -777,7 +797,7 @@ _VIDEO_SOURCE = {"rgbs": "render", "depths": "depth", "dynamic_rgbs": "render_d"
 
 def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: torch.Tensor, masks=None, num_cams: int = 3,
                    keys=("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs"), sink=None, host: bool = False,
-                   compute_metrics: bool = True, stage: str = "fine") -> Dict:
+                   compute_metrics: bool = True, stage: str = "fine", lpips=None) -> Dict:
     """The reference's evaluation loop with its videos' frames (utils/video_utils.py:116-349 render_func, then 439-499
     save_seperate_videos) from ONE render per camera: render(cam, return_decomposition=<a decomposition key is asked for>,
     extra_colors=<the frame's flow colours, if a flow key is asked for>) feeds metrics.image_metrics -- row i of the [N,5] table,
@@ -795,7 +815,9 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     then, so no frame waits for the device.  A sink receives a view of the pinned slot, valid until it returns (what a video
     writer's append_data needs); the lists and "middle" hold copies.
     -> {"psnr", "ssim", "masked_psnr", "masked_ssim", "per_frame"} as evaluate() (-1 / None with compute_metrics=False),
-    "frames", "middle", "num_timestamps".  LPIPS, file names and the encoder stay with the caller.
+    "frames", "middle", "num_timestamps".  File names and the encoder stay with the caller.
+    lpips: None, or an s3gaussian_amd.lpips.LPIPS model: as in evaluate(), the result gains "lpips" and "lpips_per_frame" (it needs
+    compute_metrics=True).
     Flow keys run the loop through render_flows (its windowing of dx and colours; stage "fine", at least 2 * num_cams cameras); they
     and the decomposition keys need the fused deformation route, as render_flows does."""
     from . import frames as _frames
@@ -822,6 +844,9 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     dev = pc.get_xyz.device
     T = N // n
     table = torch.empty((N, _metrics.RECORD), dtype=torch.float64, device=dev) if compute_metrics else None
+    if lpips is not None and not compute_metrics:
+        raise RuntimeError("evaluate_video: lpips needs compute_metrics=True")
+    lpips_table = _lpips_table(lpips, N, dev)
     result = {"frames": {k: [] for k in keys}, "middle": {}, "num_timestamps": T}
     normalize = [k == "depths" for k in keys]
     state = SimpleNamespace(strips=None, size=None, pending=None, ring={})
@@ -865,6 +890,8 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
                                f"(got {tuple(gt.shape) if torch.is_tensor(gt) else type(gt).__name__})")
         if compute_metrics:
             _metrics.image_metrics(pkg["render"], gt, None if masks is None else masks[i], out=table[i])
+            if lpips is not None:
+                _lpips.lpips(lpips, pkg["render"], gt, out=lpips_table[i])
         t, c = divmod(i, n)
         if t >= T:
             return
@@ -909,6 +936,9 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     result.update({"psnr": non_zero_mean(per_frame[:, _metrics.PSNR]), "ssim": non_zero_mean(per_frame[:, _metrics.SSIM]),
                    "masked_psnr": non_zero_mean(per_frame[contributed, _metrics.MASKED_PSNR]),
                    "masked_ssim": non_zero_mean(per_frame[contributed, _metrics.MASKED_SSIM]), "per_frame": per_frame})
+    if lpips is not None:
+        lpips_per_frame = lpips_table.cpu()
+        result.update({"lpips": non_zero_mean(lpips_per_frame[:, _lpips.TOTAL]), "lpips_per_frame": lpips_per_frame})
     return result
 
 
