@@ -9,15 +9,11 @@
 //                 sum_c w_c d_c in fp32, added per wave in double; one double per workgroup, plain stores.
 //   finalise      one workgroup adds every tap's partials in a fixed order, divides by Ho Wo, writes {total, tap0..tap4}.
 // No floating-point atomics; the two images take the same instructions whichever slot they sit in.
-#include "common.hpp"
-
-#include "../../include/s3g_lpips.h"
+#include "lpips_dev.hpp"
 
 namespace s3g {
 
-constexpr int LP_LAYERS = 5;
 constexpr int LP_BM = 128, LP_BN = 64, LP_BK = 32;   // block tile: pixels x channels, K step
-constexpr int LP_TAP_PIXELS = 8;                     // pixels per wave of the tap kernel (32 per workgroup)
 
 struct LpLayer {
   int ks, stride, pad, ci, co, pool;
@@ -30,15 +26,6 @@ constexpr int lp_kpad(int l) { return (lp_k(l) + LP_BK - 1) / LP_BK * LP_BK; }
 constexpr size_t lp_layer_floats(int l) { return (size_t)lp_kpad(l) * LP_LAYER[l].co + 2 * (size_t)LP_LAYER[l].co; }
 constexpr size_t lp_layer_offset(int l) { return l == 0 ? 0 : lp_layer_offset(l - 1) + lp_layer_floats(l - 1); }
 constexpr size_t LP_BLOB_FLOATS = lp_layer_offset(LP_LAYERS - 1) + lp_layer_floats(LP_LAYERS - 1);
-
-typedef float lp_f32x16 __attribute__((ext_vector_type(16)));
-
-// networks.py:41-44: the z-score constants are fp32 tensors
-__device__ __forceinline__ float lp_zscore(float v, int c) {
-  const float mean = c == 0 ? -.030f : (c == 1 ? -.088f : -.188f);
-  const float sd = c == 0 ? .458f : (c == 1 ? .448f : .450f);
-  return (v - mean) / sd;
-}
 
 // in0: FIRST ? image [3,Hi,Wi] planar : activations [2][Hi][Wi][CI];  in1: FIRST ? gt : unused.  out: [2][Ho][Wo][CO].
 // Bmat: [KPAD][CO].  Workgroup b owns pixel tile b / (CO/64) and channel tile b % (CO/64).
@@ -165,56 +152,6 @@ __global__ void __launch_bounds__(256) lpips_pool_kernel(int Hi, int Wi, int Ho,
   out[idx] = v;
 }
 
-__device__ __forceinline__ float lp_wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// act: [2][npix][C].  partial[blockIdx.x] = sum over this workgroup's 32 pixels of sum_c w_c (a^x_c - a^y_c)^2.
-template <int C>
-__global__ void __launch_bounds__(256) lpips_tap_kernel(int npix, const float* __restrict__ act, const float* __restrict__ lin,
-                                                        double* __restrict__ partial) {
-  constexpr int J = C / WAVE;
-  static_assert(C % WAVE == 0, "whole channel rounds per wave");
-  __shared__ double red[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float w[J];
-#pragma unroll
-  for (int j = 0; j < J; j++) w[j] = lin[j * WAVE + lane];
-  double wsum = 0.0;
-  for (int i = 0; i < LP_TAP_PIXELS; i++) {
-    const int pix = (blockIdx.x * 4 + wave) * LP_TAP_PIXELS + i;
-    if (pix >= npix) break;   // uniform over the wave
-    const float* px = act + (size_t)pix * C + lane;
-    const float* py = act + ((size_t)npix + pix) * C + lane;
-    float ax[J], ay[J], sx = 0.f, sy = 0.f;
-#pragma unroll
-    for (int j = 0; j < J; j++) {
-      ax[j] = px[j * WAVE];
-      ay[j] = py[j * WAVE];
-      sx += ax[j] * ax[j];
-      sy += ay[j] * ay[j];
-    }
-    const float nx = sqrtf(lp_wave_sum(sx)) + 1e-10f, ny = sqrtf(lp_wave_sum(sy)) + 1e-10f;   // utils.py:6-8: eps outside the root
-    float acc = 0.f;
-#pragma unroll
-    for (int j = 0; j < J; j++) {
-      const float d = ax[j] / nx - ay[j] / ny;
-      acc += w[j] * (d * d);
-    }
-    wsum += (double)lp_wave_sum(acc);
-  }
-  if (lane == 0) red[wave] = wsum;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-struct LpFinal {
-  const double* partial[LP_LAYERS];
-  int nparts[LP_LAYERS];
-  int npix[LP_LAYERS];
-};
-
 __global__ void __launch_bounds__(256) lpips_finalize_kernel(LpFinal f, double* __restrict__ record) {
   __shared__ double red[LP_LAYERS][4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -251,6 +188,15 @@ __global__ void __launch_bounds__(256) lpips_pack_kernel(int KS, int CI, int CO,
   B[idx] = v;
 }
 
+// the two launches lpips_vgg.hip shares (declared in lpips_dev.hpp, next to the tap kernel and the z-score both variants use)
+void lpips_launch_finalize(const LpFinal& f, double* record, hipStream_t stream) {
+  hipLaunchKernelGGL(lpips_finalize_kernel, dim3(1), dim3(256), 0, stream, f, record);
+}
+
+void lpips_launch_pack(int KS, int CI, int CO, int K, int KPAD, const float* w, float* B, hipStream_t stream) {
+  hipLaunchKernelGGL(lpips_pack_kernel, dim3((KPAD * CO + 255) / 256), dim3(256), 0, stream, KS, CI, CO, K, KPAD, w, B);
+}
+
 struct LpPlan {
   int Ho[LP_LAYERS], Wo[LP_LAYERS], Hp[LP_LAYERS], Wp[LP_LAYERS];   // conv outputs; the layer's pooled size (= Ho, Wo without a pool)
   float* conv[LP_LAYERS];
@@ -259,8 +205,6 @@ struct LpPlan {
   int nparts[LP_LAYERS];
   size_t bytes;
 };
-
-static inline int tap_blocks(int npix) { return (npix + 4 * LP_TAP_PIXELS - 1) / (4 * LP_TAP_PIXELS); }
 
 // H, W >= S3G_LPIPS_MIN_SIZE.  Returns false when a layer has 2^31 or more activation elements.
 static bool lpips_plan(int H, int W, void* workspace, LpPlan& p) {
@@ -340,8 +284,7 @@ extern "C" int s3g_lpips_pack_weights(const float* const conv_w[5], const float*
     const LpLayer& L = LP_LAYER[l];
     float* B = blob + lp_layer_offset(l);
     const int n = lp_kpad(l) * L.co;
-    hipLaunchKernelGGL(lpips_pack_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, L.ks, L.ci, L.co, lp_k(l), lp_kpad(l),
-                       conv_w[l], B);
+    lpips_launch_pack(L.ks, L.ci, L.co, lp_k(l), lp_kpad(l), conv_w[l], B, stream);
     S3G_HIP_CHECK(hipGetLastError());
     S3G_HIP_CHECK(hipMemcpyAsync(B + n, conv_b[l], L.co * sizeof(float), hipMemcpyDeviceToDevice, stream));
     S3G_HIP_CHECK(hipMemcpyAsync(B + n + L.co, lin_w[l], L.co * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -403,7 +346,7 @@ extern "C" int s3g_lpips(int H, int W, const float* image, const float* gt, cons
     f.nparts[l] = p.nparts[l];
     f.npix[l] = p.Ho[l] * p.Wo[l];
   }
-  hipLaunchKernelGGL(lpips_finalize_kernel, dim3(1), dim3(256), 0, stream, f, record);
+  lpips_launch_finalize(f, record, stream);
   S3G_HIP_CHECK(hipGetLastError());
   return S3G_OK;
 }

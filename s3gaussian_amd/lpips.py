@@ -51,7 +51,9 @@ def _bind():
 
 def _check_net_type(net_type):
     if net_type != "alex":
-        raise NotImplementedError(f"lpips: net_type '{net_type}' is not built; only 'alex', the variant the evaluation loop uses")
+        hint = "; the VGG16 variant is s3gaussian_amd.lpips_vgg (LPIPSVGG, lpips_vgg)" if net_type == "vgg" else ""
+        raise NotImplementedError(f"lpips: net_type '{net_type}' is not built here; only 'alex', the variant the evaluation loop "
+                                  f"uses{hint}")
 
 
 def collect_weights(alexnet_sd, lin_sd):

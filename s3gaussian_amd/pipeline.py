@@ -26,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import lpips as _lpips
+from . import lpips_vgg as _lpips_vgg
 from . import metrics as _metrics
 from .deformation import deform_network
 from .glue import activations_and_colors
@@ -642,20 +643,22 @@ def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: 
     for a camera without a dynamic mask).  The four scalars are the reference's `non_zero_mean`: the mean over the frames that
     contributed -- for the masked pair the frames with at least one masked pixel -- and -1 when none did.  "per_frame" is the
     [N,5] table on the host.
-    lpips: None, or an s3gaussian_amd.lpips.LPIPS model (the caller's weights): frame i's {total, tap0..tap4} goes into row i of an
-    [N,6] device tensor that is read back with the metrics table; the result gains "lpips" (non_zero_mean of the totals,
-    utils/video_utils.py:210, 305) and "lpips_per_frame" ([N,6] float64 on the host).  Without a model nothing changes."""
+    lpips: None, or an s3gaussian_amd.lpips.LPIPS model (AlexNet, what utils/video_utils.py reports) or an
+    s3gaussian_amd.lpips_vgg.LPIPSVGG model (VGG16, what metrics.py reports), with the caller's weights: frame i's
+    {total, tap0..tap4} goes into row i of an [N,6] device tensor that is read back with the metrics table; the result gains "lpips"
+    (non_zero_mean of the totals, utils/video_utils.py:210, 305) and "lpips_per_frame" ([N,6] float64 on the host), the same keys
+    for either model.  Without a model nothing changes."""
     n = len(cameras)
     if len(gt_images) != n or (masks is not None and len(masks) != n):
         raise RuntimeError("evaluate: one ground-truth image (and one mask entry) per camera")
     table = torch.empty((n, _metrics.RECORD), dtype=torch.float64, device=pc.get_xyz.device)
-    lpips_table = _lpips_table(lpips, n, pc.get_xyz.device)
+    lpips_fn, lpips_table = _lpips_table(lpips, n, pc.get_xyz.device)
     with torch.no_grad():
         for i, cam in enumerate(cameras):
             pkg = render(cam, pc, pipe, bg, stage=stage, return_decomposition=return_decomposition)
             _metrics.image_metrics(pkg["render"], gt_images[i], None if masks is None else masks[i], out=table[i])
             if lpips is not None:
-                _lpips.lpips(lpips, pkg["render"], gt_images[i], out=lpips_table[i])
+                lpips_fn(lpips, pkg["render"], gt_images[i], out=lpips_table[i])
     per_frame = table.cpu()
     non_zero_mean = lambda x: float(x.sum() / len(x)) if len(x) > 0 else -1      # video_utils.py:44-46
     contributed = per_frame[:, _metrics.MASKED_PIXELS] > 0
@@ -669,12 +672,17 @@ def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: 
 
 
 def _lpips_table(model, n: int, device):
-    """The [N,6] device table evaluate() and evaluate_video() fill with one lpips call per frame; None without a model."""
+    """(the per-frame call of the model's kind, the [N,6] device table evaluate() and evaluate_video() fill with it); (None, None)
+    without a model.  Both kinds write the same record."""
     if model is None:
-        return None
-    if not isinstance(model, _lpips.LPIPS):
-        raise TypeError("evaluate: lpips must be None or an s3gaussian_amd.lpips.LPIPS model")
-    return torch.empty((n, _lpips.RECORD), dtype=torch.float64, device=device)
+        return None, None
+    if isinstance(model, _lpips.LPIPS):
+        fn = _lpips.lpips
+    elif isinstance(model, _lpips_vgg.LPIPSVGG):
+        fn = _lpips_vgg.lpips_vgg
+    else:
+        raise TypeError("evaluate: lpips must be None, an s3gaussian_amd.lpips.LPIPS model or an s3gaussian_amd.lpips_vgg.LPIPSVGG model")
+    return fn, torch.empty((n, _lpips.RECORD), dtype=torch.float64, device=device)
 
 
 def _fused_route(pc: GaussianParams, pipe: SimpleNamespace) -> bool:
@@ -816,7 +824,7 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     writer's append_data needs); the lists and "middle" hold copies.
     -> {"psnr", "ssim", "masked_psnr", "masked_ssim", "per_frame"} as evaluate() (-1 / None with compute_metrics=False),
     "frames", "middle", "num_timestamps".  File names and the encoder stay with the caller.
-    lpips: None, or an s3gaussian_amd.lpips.LPIPS model: as in evaluate(), the result gains "lpips" and "lpips_per_frame" (it needs
+    lpips: None, or an LPIPS (AlexNet) or LPIPSVGG (VGG16) model: as in evaluate(), the result gains "lpips" and "lpips_per_frame" (it needs
     compute_metrics=True).
     Flow keys run the loop through render_flows (its windowing of dx and colours; stage "fine", at least 2 * num_cams cameras); they
     and the decomposition keys need the fused deformation route, as render_flows does."""
@@ -846,7 +854,7 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     table = torch.empty((N, _metrics.RECORD), dtype=torch.float64, device=dev) if compute_metrics else None
     if lpips is not None and not compute_metrics:
         raise RuntimeError("evaluate_video: lpips needs compute_metrics=True")
-    lpips_table = _lpips_table(lpips, N, dev)
+    lpips_fn, lpips_table = _lpips_table(lpips, N, dev)
     result = {"frames": {k: [] for k in keys}, "middle": {}, "num_timestamps": T}
     normalize = [k == "depths" for k in keys]
     state = SimpleNamespace(strips=None, size=None, pending=None, ring={})
@@ -891,7 +899,7 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
         if compute_metrics:
             _metrics.image_metrics(pkg["render"], gt, None if masks is None else masks[i], out=table[i])
             if lpips is not None:
-                _lpips.lpips(lpips, pkg["render"], gt, out=lpips_table[i])
+                lpips_fn(lpips, pkg["render"], gt, out=lpips_table[i])
         t, c = divmod(i, n)
         if t >= T:
             return
