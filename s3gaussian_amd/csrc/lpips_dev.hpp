@@ -1,5 +1,6 @@
 // Device code the two LPIPS variants share (lpips.hip: AlexNet, lpips_vgg.hip: VGG16): the z-score constants, the tap kernel and the
 // record layout of the finalise.  Both variants store activations [image][H][W][C], channels innermost, both images in one buffer.
+// lpips_conv.hpp, which both include, adds the layer description, the conv and pool kernels and the launch helpers on top of this.
 #pragma once
 #include "common.hpp"
 

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple, Tuple
 
 import torch
 
@@ -27,26 +28,110 @@ MIN_SIZE = 31
 FEATURE_INDEX = (0, 3, 6, 8, 10)            # torchvision's alexnet.features: the five Conv2d modules
 CONV_SHAPES = ((64, 3, 11, 11), (192, 64, 5, 5), (384, 192, 3, 3), (256, 384, 3, 3), (256, 256, 3, 3))
 
-_L = None
+
+class Variant(NamedTuple):
+    """What tells one feature stack from the other on this side of the C ABI; s3gaussian_amd.lpips_vgg holds the VGG16 one."""
+    prefix: str                             # the C symbols are {prefix}, {prefix}_weights_bytes, _pack_weights, _workspace_bytes
+    fn: str                                 # the Python function, as messages name it
+    model: str                              # the model class, as messages name it
+    net: str                                # the network, as messages name it
+    feature_index: Tuple[int, ...]          # torchvision's features.{f} of every conv
+    conv_shapes: Tuple[Tuple[int, ...], ...]
+    tap_convs: Tuple[int, ...]              # the convs tapped after their ReLU, one lin layer each
+
+
+ALEX = Variant("s3g_lpips", "lpips", "LPIPS", "AlexNet", FEATURE_INDEX, CONV_SHAPES, (0, 1, 2, 3, 4))
+
+_BOUND = {}
+
+
+def _bind_variant(v: Variant):
+    if v.prefix not in _BOUND:
+        L = _lib.lib()
+        if not hasattr(L, v.prefix):
+            raise ImportError(f"{_lib.LIB_PATH} has no {v.prefix}: it was built from an older tree: rebuild")
+        vp, i = C.c_void_p, C.c_int
+        for name, restype, argtypes in (("_weights_bytes", C.c_size_t, []),
+                                        ("_pack_weights", i, [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp]),
+                                        ("_workspace_bytes", C.c_size_t, [i, i]),
+                                        ("", i, [i, i, vp, vp, vp, vp, vp, vp])):
+            f = getattr(L, v.prefix + name)
+            f.restype, f.argtypes = restype, argtypes
+        _BOUND[v.prefix] = L
+    return _BOUND[v.prefix]
+
+
+def _collect(v: Variant, net_sd, lin_sd):
+    conv_w, conv_b, lin_w = [], [], []
+    for f, shape in zip(v.feature_index, v.conv_shapes):
+        for name in (f"features.{f}.weight", f"features.{f}.bias"):
+            if name not in net_sd:
+                raise KeyError(f"LPIPS: the {v.net} state dict has no '{name}'")
+        w, b = net_sd[f"features.{f}.weight"], net_sd[f"features.{f}.bias"]
+        if tuple(w.shape) != shape or tuple(b.shape) != shape[:1]:
+            raise RuntimeError(f"LPIPS: features.{f} has weight {tuple(w.shape)} and bias {tuple(b.shape)}, expected {shape} and "
+                               f"{shape[:1]}")
+        conv_w.append(w.detach().float())
+        conv_b.append(b.detach().float())
+    for i, conv in enumerate(v.tap_convs):
+        c = v.conv_shapes[conv][0]
+        names = (f"lin{i}.model.1.weight", f"{i}.1.weight")
+        found = [n for n in names if n in lin_sd]
+        if len(found) != 1:
+            raise KeyError(f"LPIPS: the lin state dict must hold exactly one of {names}")
+        lw = lin_sd[found[0]]
+        if tuple(lw.shape) != (1, c, 1, 1):
+            raise RuntimeError(f"LPIPS: {found[0]} has shape {tuple(lw.shape)}, expected {(1, c, 1, 1)}")
+        lin_w.append(lw.detach().float().reshape(-1))
+    return conv_w, conv_b, lin_w
+
+
+def _pack(v: Variant, net_sd, lin_sd, device) -> torch.Tensor:
+    """The state dicts' weights as the variant's blob on `device`."""
+    groups = _collect(v, net_sd, lin_sd)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"LPIPS: the weights are packed on the GPU (got {dev}); no CPU fallback")
+    L = _bind_variant(v)
+    groups = [[t.to(dev).contiguous() for t in g] for g in groups]
+    arrays = [(C.c_void_p * len(g))(*[t.data_ptr() for t in g]) for g in groups]
+    packed = torch.empty(int(getattr(L, v.prefix + "_weights_bytes")()), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):             # the device copies and the pack share the current stream: `groups` may go after it
+        _lib.check(getattr(L, v.prefix + "_pack_weights")(arrays[0], arrays[1], arrays[2], packed.data_ptr(), _lib.stream_ptr()))
+    return packed
+
+
+def _load(path):
+    return torch.load(os.path.expanduser(os.fspath(path)), weights_only=True, map_location="cpu")
+
+
+def _call(v: Variant, cls, model, image, gt, out):
+    if not isinstance(model, cls):
+        raise TypeError(f"{v.fn}: the first argument is an {v.model} model ({v.model}.from_files / {v.model}.from_state_dicts)")
+    if not (torch.is_tensor(image) and image.is_cuda and torch.is_tensor(gt) and gt.is_cuda):
+        where = image.device if torch.is_tensor(image) else type(image).__name__
+        raise RuntimeError(f"{v.fn}: images must live on the GPU (got {where}); no CPU fallback")
+    if image.dim() != 3 or image.shape[0] != 3 or gt.shape != image.shape:
+        raise RuntimeError(f"{v.fn} expects image and gt of shape [3,H,W]")
+    dev = image.device
+    if model.device != dev:
+        raise RuntimeError(f"{v.fn}: the model lives on {model.device}, the images on {dev}")
+    L = _bind_variant(v)
+    img, ref = image.detach().float().contiguous(), gt.detach().to(dev).float().contiguous()
+    _, H, W = img.shape
+    if out is None:
+        out = torch.empty(RECORD, dtype=torch.float64, device=dev)
+    elif not (out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.numel() == RECORD and out.is_contiguous()):
+        raise RuntimeError(f"{v.fn}: out must be a contiguous float64 tensor of 6 entries on the images' device")
+    work = torch.empty(max(int(getattr(L, v.prefix + "_workspace_bytes")(H, W)), 1), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(getattr(L, v.prefix)(H, W, img.data_ptr(), ref.data_ptr(), model.packed.data_ptr(), out.data_ptr(), work.data_ptr(),
+                                        _lib.stream_ptr()))
+    return out
 
 
 def _bind():
-    global _L
-    if _L is None:
-        L = _lib.lib()
-        if not hasattr(L, "s3g_lpips"):
-            raise ImportError(f"{_lib.LIB_PATH} has no s3g_lpips: it was built from an older tree: rebuild")
-        vp, i = C.c_void_p, C.c_int
-        L.s3g_lpips_weights_bytes.restype = C.c_size_t
-        L.s3g_lpips_weights_bytes.argtypes = []
-        L.s3g_lpips_pack_weights.restype = i
-        L.s3g_lpips_pack_weights.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp]
-        L.s3g_lpips_workspace_bytes.restype = C.c_size_t
-        L.s3g_lpips_workspace_bytes.argtypes = [i, i]
-        L.s3g_lpips.restype = i
-        L.s3g_lpips.argtypes = [i, i, vp, vp, vp, vp, vp, vp]
-        _L = L
-    return _L
+    return _bind_variant(ALEX)
 
 
 def _check_net_type(net_type):
@@ -60,26 +145,7 @@ def collect_weights(alexnet_sd, lin_sd):
     """-> (conv_w, conv_b, lin_w): three lists of five fp32 CPU-or-wherever tensors, shapes checked.
     alexnet_sd: torchvision's keys features.{0,3,6,8,10}.{weight,bias}; other keys (the classifier) are ignored.
     lin_sd: lin{i}.model.1.weight (upstream) or {i}.1.weight (as the reference renames them), each [1,C,1,1]."""
-    conv_w, conv_b, lin_w = [], [], []
-    for i, (f, shape) in enumerate(zip(FEATURE_INDEX, CONV_SHAPES)):
-        for name in (f"features.{f}.weight", f"features.{f}.bias"):
-            if name not in alexnet_sd:
-                raise KeyError(f"LPIPS: the AlexNet state dict has no '{name}'")
-        w, b = alexnet_sd[f"features.{f}.weight"], alexnet_sd[f"features.{f}.bias"]
-        if tuple(w.shape) != shape or tuple(b.shape) != shape[:1]:
-            raise RuntimeError(f"LPIPS: features.{f} has weight {tuple(w.shape)} and bias {tuple(b.shape)}, expected {shape} and "
-                               f"{shape[:1]}")
-        names = (f"lin{i}.model.1.weight", f"{i}.1.weight")
-        found = [n for n in names if n in lin_sd]
-        if len(found) != 1:
-            raise KeyError(f"LPIPS: the lin state dict must hold exactly one of {names}")
-        lw = lin_sd[found[0]]
-        if tuple(lw.shape) != (1, shape[0], 1, 1):
-            raise RuntimeError(f"LPIPS: {found[0]} has shape {tuple(lw.shape)}, expected {(1, shape[0], 1, 1)}")
-        conv_w.append(w.detach().float())
-        conv_b.append(b.detach().float())
-        lin_w.append(lw.detach().float().reshape(-1))
-    return conv_w, conv_b, lin_w
+    return _collect(ALEX, alexnet_sd, lin_sd)
 
 
 class LPIPS:
@@ -98,23 +164,12 @@ class LPIPS:
     @classmethod
     def from_state_dicts(cls, alexnet_sd, lin_sd, device, net_type: str = "alex"):
         _check_net_type(net_type)
-        conv_w, conv_b, lin_w = collect_weights(alexnet_sd, lin_sd)
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"LPIPS: the weights are packed on the GPU (got {dev}); no CPU fallback")
-        L = _bind()
-        groups = [[t.to(dev).contiguous() for t in g] for g in (conv_w, conv_b, lin_w)]
-        arrays = [(C.c_void_p * 5)(*[t.data_ptr() for t in g]) for g in groups]
-        packed = torch.empty(int(L.s3g_lpips_weights_bytes()), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):             # the device copies and the pack share the current stream: `groups` may go after it
-            _lib.check(L.s3g_lpips_pack_weights(arrays[0], arrays[1], arrays[2], packed.data_ptr(), _lib.stream_ptr()))
-        return cls(packed, net_type)
+        return cls(_pack(ALEX, alexnet_sd, lin_sd, device), net_type)
 
     @classmethod
     def from_files(cls, alexnet_path, lin_path, device, net_type: str = "alex"):
         _check_net_type(net_type)
-        load = lambda p: torch.load(os.path.expanduser(os.fspath(p)), weights_only=True, map_location="cpu")
-        return cls.from_state_dicts(load(alexnet_path), load(lin_path), device, net_type)
+        return cls.from_state_dicts(_load(alexnet_path), _load(lin_path), device, net_type)
 
 
 def lpips(model: LPIPS, image: torch.Tensor, gt: torch.Tensor, out=None, net_type: str = "alex"):
@@ -124,25 +179,4 @@ def lpips(model: LPIPS, image: torch.Tensor, gt: torch.Tensor, out=None, net_typ
     out: a contiguous float64 tensor of 6 entries on the same device -- one row of an [N,6] tensor -- written in place and returned.
     Nothing here waits for the device."""
     _check_net_type(net_type)
-    if not isinstance(model, LPIPS):
-        raise TypeError("lpips: the first argument is an LPIPS model (LPIPS.from_files / LPIPS.from_state_dicts)")
-    if not (torch.is_tensor(image) and image.is_cuda and torch.is_tensor(gt) and gt.is_cuda):
-        where = image.device if torch.is_tensor(image) else type(image).__name__
-        raise RuntimeError(f"lpips: images must live on the GPU (got {where}); no CPU fallback")
-    if image.dim() != 3 or image.shape[0] != 3 or gt.shape != image.shape:
-        raise RuntimeError("lpips expects image and gt of shape [3,H,W]")
-    dev = image.device
-    if model.device != dev:
-        raise RuntimeError(f"lpips: the model lives on {model.device}, the images on {dev}")
-    L = _bind()
-    img, ref = image.detach().float().contiguous(), gt.detach().to(dev).float().contiguous()
-    _, H, W = img.shape
-    if out is None:
-        out = torch.empty(RECORD, dtype=torch.float64, device=dev)
-    elif not (out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.numel() == RECORD and out.is_contiguous()):
-        raise RuntimeError("lpips: out must be a contiguous float64 tensor of 6 entries on the images' device")
-    work = torch.empty(max(int(L.s3g_lpips_workspace_bytes(H, W)), 1), dtype=torch.uint8, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(L.s3g_lpips(H, W, img.data_ptr(), ref.data_ptr(), model.packed.data_ptr(), out.data_ptr(), work.data_ptr(),
-                               _lib.stream_ptr()))
-    return out
+    return _call(ALEX, LPIPS, model, image, gt, out)

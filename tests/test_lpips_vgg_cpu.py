@@ -179,7 +179,7 @@ def test_conv_kernels_keep_their_registers_and_lds():
                           os.path.join(root, "s3gaussian_amd", "lib", "lpips_vgg.o")], capture_output=True, text=True, timeout=300).stdout
     convs = {}
     for line in out.splitlines():
-        m = re.match(r"\S*lpips_vgg_conv_kernelILi(\d+)ELi(\d+)ELi(\d+)E\S*\s+vgpr\s+(\d+).*?lds\s+(\d+)\s+scratch\s+(\d+)", line)
+        m = re.match(r"\S*lpips_conv_kernelILi3ELi1ELi1ELi(\d+)ELi(\d+)ELi(\d+)E\S*\s+vgpr\s+(\d+).*?lds\s+(\d+)\s+scratch\s+(\d+)", line)
         if m:
             convs[tuple(int(v) for v in m.groups()[:3])] = tuple(int(v) for v in m.groups()[3:])
     assert set(convs) == {(3, 64, 64), (64, 64, 64), (64, 128, 128), (128, 128, 128), (128, 256, 128), (256, 256, 128),
@@ -187,3 +187,16 @@ def test_conv_kernels_keep_their_registers_and_lds():
     for (ci, co, bn), (vgpr, lds, scratch) in convs.items():
         assert scratch == 0 and lds == 2 * 32 * (128 + bn) * 4, (ci, co, bn, vgpr, lds, scratch)
         assert vgpr <= 256 and (bn == 128 or vgpr <= 168), (ci, co, bn, vgpr)      # vgpr counts the accumulators' AGPRs too
+    # the AlexNet variant instantiates the same kernel, always at BN = 64
+    out = subprocess.run(["bash", os.path.join(root, "tools", "kernel_resources.sh"),
+                          os.path.join(root, "s3gaussian_amd", "lib", "lpips.o")], capture_output=True, text=True, timeout=300).stdout
+    alex = {}
+    for line in out.splitlines():
+        m = re.match(r"\S*lpips_conv_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E\S*\s+vgpr\s+(\d+).*?lds\s+(\d+)\s+scratch\s+(\d+)",
+                     line)
+        if m:
+            alex[tuple(int(v) for v in m.groups()[:6])] = tuple(int(v) for v in m.groups()[6:])
+    assert set(alex) == {(11, 4, 2, 3, 64, 64), (5, 1, 2, 64, 192, 64), (3, 1, 1, 192, 384, 64), (3, 1, 1, 384, 256, 64),
+                         (3, 1, 1, 256, 256, 64)}, out
+    for key, (vgpr, lds, scratch) in alex.items():
+        assert scratch == 0 and lds == 49152 and vgpr <= 168, (key, vgpr, lds, scratch)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Evaluation LPIPS: one s3gaussian_amd.lpips call against the same arithmetic on torch ops, on the same device.
 
-  hip       lpips(model, image, gt): csrc/lpips.hip, 14 launches, weights packed once.
+  hip       lpips(model, image, gt): csrc/lpips.hip over csrc/lpips_conv.hpp, 14 launches, weights packed once.
   torch     F.conv2d / F.max_pool2d and the normalisation on torch ops, fp32, both images as one batch of 2, weights moved to the
             device ONCE -- kinder to it than the reference's lpips(), which builds the network and reloads both weight files on
             every call (lpipsPyTorch/__init__.py:19-21).
@@ -89,7 +89,7 @@ def conv_table(directory, H, W):
     lines = [f"# per-convolution time and achieved TF against the {PEAK_TF} TF fp32 matrix peak ({H} x {W}, from {os.path.basename(f[0])})"]
     sizes = layer_sizes(H, W)
     for l, (co, ci, k, stride, pad, _) in enumerate(lr.LAYERS):
-        tag = f"lpips_conv_kernel<{k}, {stride}, {pad}, {ci}, {co},"
+        tag = f"lpips_conv_kernel<{k}, {stride}, {pad}, {ci}, {co}, 64,"
         hit = [r for n, r in rows.items() if tag in n]
         if not hit:
             lines.append(f"conv{l + 1}: not in the trace")

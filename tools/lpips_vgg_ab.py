@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Evaluation LPIPS, VGG16 variant: one s3gaussian_amd.lpips_vgg call against the same arithmetic on torch ops, on the same device.
 
-  hip       lpips_vgg(model, image, gt): csrc/lpips_vgg.hip, 24 launches, weights packed once.
+  hip       lpips_vgg(model, image, gt): csrc/lpips_vgg.hip over csrc/lpips_conv.hpp, 24 launches, weights packed once.
   torch     F.conv2d / F.max_pool2d and the normalisation on torch ops, fp32, both images as one batch of 2, weights moved to the
             device ONCE -- kinder to it than the reference's lpips(), which builds the network and reloads both weight files on
             every call (lpipsPyTorch/__init__.py:19-21).  Its backend is free to choose a convolution algorithm (Winograd, say) that
@@ -88,7 +88,7 @@ def layer_table(directory, H, W):
     rows = [r for r in csv.DictReader(open(f[0])) if "lpips" in r["Kernel_Name"] and "pack" not in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-    convs = [dur(r) for r in rows if "lpips_vgg_conv_kernel" in r["Kernel_Name"]]
+    convs = [dur(r) for r in rows if "lpips_conv_kernel" in r["Kernel_Name"]]
     calls = len(convs) // 13
     assert calls > 0 and len(convs) == 13 * calls, len(convs)
     per_layer = np.array(convs).reshape(calls, 13)
@@ -100,7 +100,7 @@ def layer_table(directory, H, W):
         tf = sizes[l][2] / (us * 1e-6) / 1e12
         lines.append(f"{NAMES[l]} {ci:3d} -> {co:3d} at {sizes[l][0]:4d} x {sizes[l][1]:4d}: {us:8.1f} us  {sizes[l][2] / 1e9:7.2f} GFLOP  "
                      f"{tf:6.1f} TF  {100 * tf / PEAK_TF:5.1f} % of peak")
-    for tag in ("lpips_vgg_front_kernel", "lpips_vgg_pool_kernel", "lpips_tap_kernel", "lpips_finalize_kernel"):
+    for tag in ("lpips_vgg_front_kernel", "lpips_pool_kernel", "lpips_tap_kernel", "lpips_finalize_kernel"):
         us = sum(dur(r) for r in rows if tag in r["Kernel_Name"]) / calls
         lines.append(f"{tag}: {us:8.1f} us per call")
     total = sum(dur(r) for r in rows) / calls / 1e3
