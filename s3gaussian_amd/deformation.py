@@ -8,6 +8,8 @@ out).  Every other switch of scene/deformation.py:16-178 is honoured too -- no_d
 feat_head, grid_pe (sin/cos embedding of the grid feature, :84-86), no_grid (:79-80), static_mlp and empty_voxel (the
 per-point mask of :108-114, DenseGrid of scene/grid.py:15-42), apply_rotation (:140-141) -- on the same fused sampler with
 the heads as PyTorch-ROCm library GEMMs (GPU only; nothing here runs on the CPU).
+With any of no_ds / no_dr / no_do off (scale, rotation, opacity deformation) the plain-grid configuration stays on the fused route:
+those heads run as a second fused operator beside the MLP (mlp_geom.geometry_heads, `_fused_geometry_ok`).
 """
 from __future__ import annotations
 
@@ -20,6 +22,7 @@ from .hexplane import HexPlaneField
 import os
 
 from .mlp import deform_infer, deform_mlp
+from .mlp_geom import geometry_heads
 
 # S3G_FUSED_INFERENCE=0: inference renders go through the two separate kernels (sampler, then MLP) like training does
 FUSED_INFERENCE = os.environ.get("S3G_FUSED_INFERENCE", "1") != "0"
@@ -133,17 +136,38 @@ class Deformation(nn.Module):
             return self.forward_static(rays_pts_emb[:, :3])
         return self.forward_dynamic(rays_pts_emb, scales_emb, rotations_emb, opacity, shs_emb, time_feature, time_emb)
 
+    def _mlp_kernels_fit(self):
+        """What the fused MLP kernels are built for: a plain grid (per-point mask 1), D == 1, W == 64, 128 features, the dshs and
+        feature heads on; no_dx either way."""
+        a = self.args
+        plain = not (self.no_grid or self.grid_pe != 0 or getattr(a, "static_mlp", False) or getattr(a, "empty_voxel", False))
+        return bool(plain and self.D == 1 and self.W == 64 and self.grid.feat_dim == 128 and not a.no_dshs and a.feat_head)
+
     def _fused_ok(self):
         """The fused route serves the reference's default heads (dx + dshs + feat) and the static configuration (no_dx: dshs + feat)."""
         a = self.args
-        plain = not (self.no_grid or self.grid_pe != 0 or getattr(a, "static_mlp", False) or getattr(a, "empty_voxel", False))
-        return (plain and self.D == 1 and self.W == 64 and self.grid.feat_dim == 128 and not a.no_dshs
-                and a.no_ds and a.no_dr and a.no_do and a.feat_head)
+        return bool(self._mlp_kernels_fit() and a.no_ds and a.no_dr and a.no_do)
 
-    def deform_heads(self, xyz, time, uniform_time=None, reg_weights=None, need_feat=True):
+    def _fused_geometry_ok(self):
+        """The fused route with the geometry heads beside it (mlp_geom.geometry_heads): at least one of the scale / rotation / opacity
+        heads is on and everything else `_fused_ok` asks for holds.  Never true together with `_fused_ok`, which keeps its meaning: the
+        configurations the MLP kernels serve on their own."""
+        a = self.args
+        return bool(self._mlp_kernels_fit() and not (a.no_ds and a.no_dr and a.no_do))
+
+    def _geometry_modules(self):
+        """(scales_deform, rotations_deform, opacity_deform) with None for a head the configuration switches off."""
+        a = self.args
+        return (None if a.no_ds else self.scales_deform, None if a.no_dr else self.rotations_deform,
+                None if a.no_do else self.opacity_deform)
+
+    def deform_heads(self, xyz, time, uniform_time=None, reg_weights=None, need_feat=True, with_geometry=False):
         """(dx [P,3], dshs [P,16,3], feat [P,3]) only -- the part of forward_dynamic that is not a pass-through in the
         reference's default configuration.  Lets a caller that fuses `shs + dshs` downstream (pipeline.render) skip
-        materialising the [P,16,3] sum.  dx is None for a no_dx network (static scenes): the position head is never evaluated."""
+        materialising the [P,16,3] sum.  dx is None for a no_dx network (static scenes): the position head is never evaluated.
+        with_geometry=True: one more entry, (ds [P,3], dr [P,4], do [P,1]) -- the outputs of the scale / rotation / opacity heads of a
+        `_fused_geometry_ok` network, None for a head that is off -- or None for a network without them; it sits in front of the
+        regulariser's entry."""
         global infer_cache_hits
         key = None
         if INFER_CACHE and not torch.is_grad_enabled() and reg_weights is None and xyz.is_cuda:
@@ -156,9 +180,10 @@ class Deformation(nn.Module):
             hit = self.__dict__.get("_infer_cache")
             if hit is not None and hit[0] == key and all(t._version == v for t, v in hit[2]):   # (a consumer edited dx in place: miss)
                 infer_cache_hits += 1
-                return hit[1]
+                return self._heads_result(hit[1], with_geometry)
         need_dx = not self.args.no_dx
-        if (FUSED_INFERENCE and need_dx and not torch.is_grad_enabled() and not need_feat and reg_weights is None and xyz.is_cuda
+        geometry = self._fused_geometry_ok()
+        if (FUSED_INFERENCE and need_dx and not geometry and not torch.is_grad_enabled() and not need_feat and reg_weights is None and xyz.is_cuda
                 and len(self.grid.resolutions) == 4):
             # inference render without the feature image: sampler (+) heads in one kernel, no [P,128] round trip
             dx, dshs = deform_infer(self.grid, xyz[:, :3], time[:, :1], self.feature_out, self.pos_deform, self.shs_deform,
@@ -166,19 +191,30 @@ class Deformation(nn.Module):
             out = (dx, dshs.reshape([xyz.shape[0], 16, 3]), None)
             if key is not None:
                 self._keep_inference(key, out, xyz, time)
-            return out
+            return self._heads_result(out, with_geometry)
         reg = None
         if reg_weights is not None:   # plane regulariser evaluated on the sampler's autograd node (hexplane_sample)
             feats, reg = self.grid(xyz[:, :3], time[:, :1], uniform_time, reg_weights)
         else:
             feats = self.grid(xyz[:, :3], time[:, :1], uniform_time)
         # need_feat=False (honoured only when no backward follows): skip the feature head, `feat` is then None
-        # (a no_dx network's no_grad renders take these two kernels too: the one-kernel route has no variant without the head)
+        # (a no_dx network's no_grad renders take these two kernels too: the one-kernel route has no variant without the head; so do
+        #  those of a network with geometry heads, which are a third kernel on the same features)
         dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, self.dino_head, need_feat, need_dx)
         out = (dx, dshs.reshape([xyz.shape[0], 16, 3]), feat)
+        if geometry:             # the cached evaluation carries ds / dr / do behind the three
+            out = out + tuple(geometry_heads(feats, self.feature_out, *self._geometry_modules()))
         if key is not None:      # (no_grad, no regulariser: what an evaluation render with the feature image asks for)
             self._keep_inference(key, out, xyz, time)
+        out = self._heads_result(out, with_geometry)
         return out + (reg,) if reg_weights is not None else out
+
+    @staticmethod
+    def _heads_result(out, with_geometry):
+        """What deform_heads hands out of an evaluation `out` = (dx, dshs, feat) or (dx, dshs, feat, ds, dr, do)."""
+        if not with_geometry:
+            return out if len(out) == 3 else out[:3]
+        return out[:3] + (tuple(out[3:]) if len(out) > 3 else None,)
 
     def _keep_inference(self, key, out, xyz, time) -> None:
         """ONE entry (the last timestamp): dx 14 MB + dshs 230 MB (+ feat 14 MB) at 1.2 M Gaussians.  xyz / time are kept alive so
@@ -205,14 +241,20 @@ class Deformation(nn.Module):
 
     def forward_dynamic(self, rays_pts_emb, scales_emb, rotations_emb, opacity_emb, shs_emb, time_feature, time_emb):
         a = self.args
-        if self._fused_ok() and rays_pts_emb.is_cuda:
+        geometry = self._fused_geometry_ok()
+        if (geometry or self._fused_ok()) and rays_pts_emb.is_cuda:
             # reference default configuration: HexPlane sampler -> one fused MFMA MLP kernel (include/s3g_mlp.h)
             feats = self.grid(rays_pts_emb[:, :3], time_emb[:, :1])
             dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, self.dino_head, need_dx=not a.no_dx)
             dshs = dshs.reshape([shs_emb.shape[0], 16, 3])
             pts = rays_pts_emb[:, :3] if dx is None else rays_pts_emb[:, :3] + dx     # no_dx: scene/deformation.py:119-121
-            return (pts, scales_emb[:, :3], rotations_emb[:, :4], opacity_emb[:, :1], shs_emb + dshs,
-                    dx, feat, dshs)
+            scales, rotations, opacity = scales_emb[:, :3], rotations_emb[:, :4], opacity_emb[:, :1]
+            if geometry:
+                # scale / rotation / opacity heads: a second fused node on the same features (include/s3g_mlp_geom.h); the per-point
+                # mask of scene/deformation.py:108-114 is 1 in every configuration admitted here
+                ds, dr, do = geometry_heads(feats, self.feature_out, *self._geometry_modules())
+                scales, rotations, opacity = self.apply_geometry(scales, rotations, opacity, ds, dr, do)
+            return (pts, scales, rotations, opacity, shs_emb + dshs, dx, feat, dshs)
         # other switch combinations: fused HexPlane sampler + library GEMMs, scene/deformation.py:106-166 line by line
         hidden = self.query_time(rays_pts_emb, scales_emb, rotations_emb, time_feature, time_emb)
         if getattr(a, "static_mlp", False):
@@ -240,6 +282,17 @@ class Deformation(nn.Module):
         if a.feat_head:
             feat = self.dino_head(hidden)
         return pts, scales, rotations, opacity, shs, dx, feat, dshs
+
+    def apply_geometry(self, scales, rotations, opacity, ds, dr, do):
+        """scene/deformation.py:126-152 with mask = 1: scales + ds, rotations + dr (the normalised quaternion product with
+        apply_rotation), opacity + do; a head that is off (None) leaves its input as it is."""
+        if ds is not None:
+            scales = scales + ds
+        if dr is not None:
+            rotations = batch_quaternion_multiply(rotations, dr) if getattr(self.args, "apply_rotation", False) else rotations + dr
+        if do is not None:
+            opacity = opacity + do
+        return scales, rotations, opacity
 
     def get_mlp_parameters(self):
         return [p for n, p in self.named_parameters() if "grid" not in n]

@@ -464,7 +464,7 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
     hy = net.args
     glue_ok = (means3D.is_cuda and override_color is None and getattr(pipe, "convert_SHs_python", True)
                and pc.max_sh_degree == 3 and getattr(pipe, "fused_glue", True))   # pipe.fused_glue=False: torch glue (tests)
-    fused_glue = glue_ok and ("coarse" in stage or net._fused_ok())
+    fused_glue = glue_ok and ("coarse" in stage or net._fused_ok() or net._fused_geometry_ok())
     if "coarse" in stage:
         means3D_final, scales_final, rotations_final, opacity_final = means3D, scales, rotations, opacity
         if not fused_glue:
@@ -478,10 +478,14 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
             regw = ((hy.time_smoothness_weight, hy.l1_time_planes, hy.plane_tv_weight)
                     if (stage == "fine" and torch.is_grad_enabled() and hy.time_smoothness_weight != 0) else None)
             heads = net.deform_heads(means3D, _uniform_time(float(cam["time"]), dev), uniform_time=True, reg_weights=regw,
-                                     need_feat=render_feat or torch.is_grad_enabled())
+                                     need_feat=render_feat or torch.is_grad_enabled(), with_geometry=True)
             dx, dshs, feat = heads[:3]
-            plane_reg = heads[3] if regw is not None else None
+            plane_reg = heads[4] if regw is not None else None
             means3D_final = means3D if dx is None else means3D + dx     # dx is None: a static model (no_dx) has no position head
+            if heads[3] is not None:
+                # scale / rotation / opacity deformation (no_ds / no_dr / no_do off): the raw parameters plus the geometry heads' outputs
+                # go into the glue kernel in place of the raw ones (deformation.py:126-152, then the activations of :99-101)
+                scales, rotations, opacity = net.apply_geometry(scales, rotations, opacity, *heads[3])
             scales_final, rotations_final, opacity_final = scales, rotations, opacity
         else:
             time = torch.full((means3D.shape[0], 1), float(cam["time"]), device=dev)
@@ -688,9 +692,10 @@ def _lpips_table(model, n: int, device):
 def _fused_route(pc: GaussianParams, pipe: SimpleNamespace) -> bool:
     """render() takes the fused deformation route for this model AND the model has a position head (a static model, no_dx=True,
     takes the route too, but produces no dx: nothing to colour a flow with or to split dynamic from static by): GPU tensors, the
-    default head configuration, SH degree 3, convert_SHs_python and fused_glue on."""
+    default head configuration (with or without the scale / rotation / opacity heads: Deformation._fused_geometry_ok), SH degree 3,
+    convert_SHs_python and fused_glue on."""
     net = pc._deformation.deformation_net
-    return bool(pc.get_xyz.is_cuda and net._fused_ok() and not net.args.no_dx and pc.max_sh_degree == 3
+    return bool(pc.get_xyz.is_cuda and (net._fused_ok() or net._fused_geometry_ok()) and not net.args.no_dx and pc.max_sh_degree == 3
                 and getattr(pipe, "convert_SHs_python", True) and getattr(pipe, "fused_glue", True))
 
 
@@ -793,7 +798,7 @@ def save_split_point_clouds(pc: GaussianParams, time: float, dynamic_pcd_path: s
     if "fine" not in stage:
         raise RuntimeError(f"save_split_point_clouds: stage {stage!r} has no deformation; only the fine stage has a dx")
     xyz = pc.get_xyz
-    if not (xyz.is_cuda and net._fused_ok()):
+    if not (xyz.is_cuda and (net._fused_ok() or net._fused_geometry_ok())):
         raise RuntimeError("save_split_point_clouds needs GPU tensors and the default head configuration (dx + dshs + feature head)")
     dx = net.deform_heads(xyz, _uniform_time(float(time), xyz.device), uniform_time=True, reg_weights=None, need_feat=False)[0]
     return split.export_split(pc, dx, dynamic_pcd_path, static_pcd_path)
