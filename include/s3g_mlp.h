@@ -44,8 +44,16 @@ size_t s3g_deform_mlp_pack_bytes(void);
  * dx may be NULL (static scenes, ModelHiddenParams no_dx=True: scene/deformation.py:119-121 never calls the head): the position
  * head is skipped -- P1, its ReLU, P2 and the dx store are not computed, and with save_activations != 0 stash plane 1 (pos1) and
  * mask word 1 of every tile are left unwritten.  dshs, feat and every other stash plane / mask word are bit for bit what the call
- * writes with a non-NULL dx.  Combines with feat == NULL (then save_activations must be 0, as above).  w->P1..pb2 stay valid
- * pointers in every case: the weight images are packed whole. */
+ * writes with a non-NULL dx.  Combines with feat == NULL.  w->P1..pb2 stay valid pointers in every case: the weight images are
+ * packed whole.
+ * feat == NULL with save_activations != 0 is valid too (a network without a feature head, ModelHiddenParams feat_head=False): stash
+ * planes 3 and 4 (dino1, dino2) and mask words 3 and 4 of every tile are left unwritten, and the backward must be given g_feat == NULL.
+ * w->D0..db2 stay valid pointers (a zero block will do).
+ * dshs may be NULL (no_dshs=True): no S1, no ReLU, no S2 and no [P,48] store; stash plane 2 (shs1) and mask word 2 stay unwritten.
+ * These calls run the exact fp32 MFMA chain in EVERY arithmetic mode below (csrc/mlp_heads.hip); in S3G_MLP_F32 dx and feat are bit
+ * for bit what the call writes with a non-NULL dshs.  Combines with dx == NULL or feat == NULL, but at least one of the three outputs
+ * must be given: with P > 0 a call whose dx, dshs and feat are all NULL returns S3G_ERR_INVALID_ARG (P == 0 returns S3G_OK before
+ * looking at them). */
 int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const float* features, float* dx, float* dshs, float* feat,
                            float* stash, int save_activations, void* stream);
 
@@ -56,7 +64,13 @@ int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const float* features
  * backward is skipped and gw->D0..db2 are left untouched, like autograd leaving those parameters' .grad at None.
  * g_dx may be NULL = the forward ran with dx == NULL: the position head's backward is skipped -- no read of g_dx, of mask word 1 or of
  * stash plane 1, workspace plane 2 (the pos1 signal) is not written -- and gw->P1, pb1, P2, pb2 are left untouched and may be NULL.
- * All four combinations of g_dx / g_feat being NULL or not are valid (s3g_deform_mlp_backward_ordered alike). */
+ * g_dshs may be NULL = the forward ran with dshs == NULL: the exact fp32 chain without the SH head, in every arithmetic mode -- no
+ * read of g_dshs, of mask word 2 or of stash plane 2, workspace plane 3 (the shs1 signal) is not written -- and gw->S1, sb1, S2, sb2
+ * are left untouched and may be NULL; s3g_deform_mlp_wgrad_partial_bytes() stays an upper bound.  In S3G_MLP_F32 the results are
+ * those of the call fed an all-zero g_dshs.
+ * Every combination of g_dx / g_dshs / g_feat being NULL or not is valid except all three NULL, which (with P > 0) returns
+ * S3G_ERR_INVALID_ARG, as does a NULL gw->W0 / b0 or a NULL gw slot of a head whose upstream gradient is given
+ * (s3g_deform_mlp_backward_ordered alike). */
 int s3g_deform_mlp_backward(const s3g_mlp_params* w, int P, const float* features, const float* stash, const float* g_dx,
                             const float* g_dshs, const float* g_feat, float* g_features, const s3g_mlp_params* gw,
                             float* workspace, void* stream);

@@ -20,7 +20,8 @@
 //   mlp_forward_presplit_kernel / mlp_backward_presplit_kernel   the same bf16 x 3 arithmetic on weight images split ONCE by
 //                        mlp_pack_presplit_fwd_kernel / _bwd_kernel (layouts tpw / tbw below), bit-identical to <true> -- S3G_MLP_BF16X3.
 // The weight gradients (K dimension = the points) are mlp_wgrad.hip, reached through mlp_wgrad_launch(); the fused sampler (+) MLP
-// inference kernel is deform_infer.hip.
+// inference kernel is deform_infer.hip; the chain kernels without the SH head (dshs / g_dshs == NULL) are mlp_heads.hip, reached
+// through mlp_nosh_forward_launch() / mlp_nosh_backward_launch().
 // HBM scratch is spent freely (2 x 1280 B per point): 3 GB of the 288 GB, ~1 ms of traffic for ~20 ms saved.
 #include "mlp_dev.hpp"
 
@@ -866,13 +867,27 @@ static int mlp_set_attrs() {
 
 extern "C" int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const float* features, float* dx, float* dshs,
                                       float* feat, float* stash, int save_activations, void* stream_) {
-  if (!w || P < 0 || (P > 0 && (!features || !dshs || !stash || (!feat && save_activations)))) {
+  if (!w || P < 0 || (P > 0 && (!features || !stash))) {
     set_error("s3g_deform_mlp_forward: bad argument");
     return S3G_ERR_INVALID_ARG;
   }
+  if (P > 0 && !dx && !dshs && !feat) {
+    set_error("s3g_deform_mlp_forward: dx, dshs and feat are all NULL: no head to compute");
+    return S3G_ERR_INVALID_ARG;
+  }
   if (P == 0) return S3G_OK;
-  if (int e = mlp_set_attrs()) return e;
   hipStream_t stream = (hipStream_t)stream_;
+  if (!dshs) {   // no SH head (no_dshs): the exact fp32 family of mlp_heads.hip on the fp32 image, whatever the arithmetic mode
+    mlp_pack_launch(*w, stash, stream);
+    profile_begin(S3G_PROFILE_MLP_FORWARD, stream);
+    float* planes = save_activations ? stash + PACK_TOTAL : nullptr;
+    uint32_t* words = save_activations ? reinterpret_cast<uint32_t*>(stash + PACK_TOTAL + (size_t)5 * P * HID) : nullptr;
+    if (int e = mlp_nosh_forward_launch(P, features, stash, dx, feat, planes, words, stream)) return e;
+    profile_end(S3G_PROFILE_MLP_FORWARD, stream, (double)P, 0.0);
+    S3G_HIP_CHECK(hipGetLastError());
+    return S3G_OK;
+  }
+  if (int e = mlp_set_attrs()) return e;
   MlpFwdArgs a;
   a.P = P; a.x = features; a.packed = stash; a.dx = dx; a.dshs = dshs; a.feat = feat;
   a.stash = save_activations ? stash + PACK_TOTAL : nullptr;
@@ -909,14 +924,38 @@ extern "C" int s3g_deform_mlp_forward(const s3g_mlp_params* w, int P, const floa
 static int mlp_backward_impl(const s3g_mlp_params* w, int P, const float* features, const float* stash_, const float* g_dx,
                              const float* g_dshs, const float* g_feat, float* g_features, const s3g_mlp_params* gw, float* workspace,
                              float* partials, void* stream_) {
-  if (!w || !gw || P < 0 || (P > 0 && (!features || !stash_ || !g_dshs || !g_features || !workspace))) {
+  if (!w || !gw || P < 0 || (P > 0 && (!features || !stash_ || !g_features || !workspace))) {
     set_error("s3g_deform_mlp_backward: bad argument");
     return S3G_ERR_INVALID_ARG;
   }
+  if (P > 0 && !g_dx && !g_dshs && !g_feat) {
+    set_error("s3g_deform_mlp_backward: g_dx, g_dshs and g_feat are all NULL: no head to differentiate");
+    return S3G_ERR_INVALID_ARG;
+  }
+  if (P > 0 && (!gw->W0 || !gw->b0 || (g_dx && (!gw->P1 || !gw->pb1 || !gw->P2 || !gw->pb2)) ||
+                (g_dshs && (!gw->S1 || !gw->sb1 || !gw->S2 || !gw->sb2)) ||
+                (g_feat && (!gw->D0 || !gw->db0 || !gw->D1 || !gw->db1 || !gw->D2 || !gw->db2)))) {
+    set_error("s3g_deform_mlp_backward: gw has a NULL slot for feature_out or for a head whose upstream gradient is given");
+    return S3G_ERR_INVALID_ARG;
+  }
   if (P == 0) return S3G_OK;
-  if (int e = mlp_set_attrs()) return e;
   hipStream_t stream = (hipStream_t)stream_;
   const float* stash = stash_ + PACK_TOTAL;  // activations; the packed weight images of the forward sit in front
+  if (!g_dshs) {   // no SH head: mlp_heads.hip's exact fp32 chain on the fp32 image (packed here: a forward in another process-wide mode
+                   // would not have; only the image region of the caller's buffer is written), then the job table without the two SH jobs
+    mlp_pack_launch(*w, const_cast<float*>(stash_), stream);
+    profile_begin(S3G_PROFILE_MLP_BACKWARD, stream);
+    if (int e = mlp_nosh_backward_launch(P, stash_, reinterpret_cast<const uint32_t*>(stash + (size_t)5 * P * HID), g_dx, g_feat, g_features,
+                                         workspace, stream))
+      return e;
+    profile_end(S3G_PROFILE_MLP_BACKWARD, stream, (double)P, 0.0);
+    S3G_HIP_CHECK(hipGetLastError());
+    profile_begin(S3G_PROFILE_MLP_WGRAD, stream);
+    if (int e = mlp_wgrad_launch(P, features, stash, workspace, g_dx, nullptr, g_feat, gw, partials, stream)) return e;
+    profile_end(S3G_PROFILE_MLP_WGRAD, stream, (double)P, 0.0);
+    return S3G_OK;
+  }
+  if (int e = mlp_set_attrs()) return e;
   MlpBwdArgs b;
   b.P = P; b.packed = stash_; b.maskbits = reinterpret_cast<const uint32_t*>(stash + (size_t)5 * P * HID); b.g_dx = g_dx; b.g_dshs = g_dshs; b.g_feat = g_feat; b.g_x = g_features; b.ws = workspace;
   const int ntiles = (P + MT - 1) / MT;

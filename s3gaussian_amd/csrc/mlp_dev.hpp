@@ -1,5 +1,6 @@
-// Device helpers shared by the three kernel families of the deformation MLP, and the host functions that cross their files:
+// Device helpers shared by the kernel families of the deformation MLP, and the host functions that cross their files:
 //   mlp.hip           the per-point chain kernels (forward / backward, exact fp32 and bf16 x 3) and their weight-image pack kernels
+//   mlp_heads.hip     the per-point chain kernels without the SH head (exact fp32)
 //   mlp_wgrad.hip     the weight-gradient kernels (K dimension = the points)
 //   deform_infer.hip  the fused HexPlane sampler (+) MLP inference kernel
 // Here: the tile constants, the accumulator-layout helpers of v_mfma_f32_32x32x2_f32 (activations stay in the accumulator registers
@@ -379,5 +380,12 @@ void mlp_pack_launch(const s3g_mlp_params& w, float* packed, hipStream_t stream)
 // atomics; else the s3g_deform_mlp_wgrad_partial_bytes() buffer of the ordered (bit-reproducible) flush.
 int mlp_wgrad_launch(int P, const float* features, const float* stash, const float* signals, const float* g_dx, const float* g_dshs,
                      const float* g_feat, const s3g_mlp_params* gw, float* partials, hipStream_t stream);
+// mlp_heads.hip: the chain kernels without the SH head (dshs / g_dshs == NULL), exact fp32 in every arithmetic mode.  `packed` = the fp32
+// image of mlp_pack_launch; `planes` / `maskbits` = the stash's five activation planes and its mask words (both NULL when no backward
+// follows); dx / feat and g_dx / g_feat: either may be NULL, not both.
+int mlp_nosh_forward_launch(int P, const float* features, const float* packed, float* dx, float* feat, float* planes, uint32_t* maskbits,
+                            hipStream_t stream);
+int mlp_nosh_backward_launch(int P, const float* packed, const uint32_t* maskbits, const float* g_dx, const float* g_feat, float* g_features,
+                             float* workspace, hipStream_t stream);
 
 }  // namespace s3g

@@ -4,8 +4,8 @@
 // HBM: at K step s lane (i, k) supplies point p0 + 2s + k, and -- because the order of the M / N rows of an MFMA is as free as its
 // K order -- row i of block t is feature 2*i + t, so a lane's operand values for both blocks are ONE contiguous 8-byte load and a
 // wave instruction reads two whole rows.  No operand goes through LDS, nothing is transposed.
-//   mlp_wgrad_all_kernel     all eight (six without the dino head; seven / four without the position head) GEMMs of a backward pass in
-//                            one launch, one wave per GEMM
+//   mlp_wgrad_all_kernel     all eight (six without the dino head; seven / four without the position head; six / five / four without
+//                            the SH head) GEMMs of a backward pass in one launch, one wave per GEMM
 //   mlp_wgrad_reduce_kernel  second half of the ordered flush: the workgroups' partial blocks summed in block order
 //   mlp_wgrad_launch()       builds the job table from the stash / signal planes; called by mlp.hip's backward
 // Software pipeline of a wave: the operand rows of its NEXT tile are requested before the 64 MFMAs of the current tile are issued
@@ -348,6 +348,21 @@ int mlp_wgrad_launch(int P, const float* features, const float* stash, const flo
   const WJobX p1 = wide(signals + 2 * PS, stash + 0 * PS, gw->P1, gw->pb1, HID, RELU);   // (unused when g_dx == NULL: gw->P1 may be NULL)
   const WJobX s1 = wide(signals + 3 * PS, stash + 0 * PS, gw->S1, gw->sb1, HID, RELU);
   const WJobX s2 = wide(g_dshs, stash + 2 * PS, gw->S2, gw->sb2, HID, NONE, 48);
+  if (g_dshs == nullptr) {   // no SH head (mlp_heads.hip's chain): the table without s1 / s2; gw->S1..sb2 untouched and may be NULL
+    WJobX head{g_dx, stash + 1 * PS, gw->P2, gw->pb2, 3, 3, HID, NONE, 1, nullptr, nullptr, nullptr, nullptr};
+    if (g_dx != nullptr && g_feat != nullptr) {
+      head.G2 = g_feat; head.A2 = stash + 4 * PS; head.dW2 = gw->D2; head.db2 = gw->db2;
+      const WJobX jobs[6] = {w0a, w0b, d0, p1, d1, head};
+      return launch_wgrad_all(jobs, 6, P, stream, partials);
+    }
+    if (g_dx != nullptr) {
+      const WJobX jobs[4] = {w0a, w0b, p1, head};
+      return launch_wgrad_all(jobs, 4, P, stream, partials);
+    }
+    const WJobX fhead{g_feat, stash + 4 * PS, gw->D2, gw->db2, 3, 3, HID, NONE, 1, nullptr, nullptr, nullptr, nullptr};
+    const WJobX jobs[5] = {w0a, w0b, d0, d1, fhead};
+    return launch_wgrad_all(jobs, 5, P, stream, partials);
+  }
   if (g_dx == nullptr) {   // no position head (static scenes): no p1 job, gw->P1..pb2 untouched; the head job carries g_feat / D2 alone
     if (g_feat != nullptr) {
       const WJobX head{g_feat, stash + 4 * PS, gw->D2, gw->db2, 3, 3, HID, NONE, 1, nullptr, nullptr, nullptr, nullptr};

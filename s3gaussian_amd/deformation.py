@@ -9,7 +9,9 @@ feat_head, grid_pe (sin/cos embedding of the grid feature, :84-86), no_grid (:79
 per-point mask of :108-114, DenseGrid of scene/grid.py:15-42), apply_rotation (:140-141) -- on the same fused sampler with
 the heads as PyTorch-ROCm library GEMMs (GPU only; nothing here runs on the CPU).
 With any of no_ds / no_dr / no_do off (scale, rotation, opacity deformation) the plain-grid configuration stays on the fused route:
-those heads run as a second fused operator beside the MLP (mlp_geom.geometry_heads, `_fused_geometry_ok`).
+those heads run as a second fused operator beside the MLP (mlp_geom.geometry_heads, `_fused_geometry_ok`).  So does it with no_dshs on
+or feat_head off (`_fused_heads_ok`): every on/off combination of the six heads runs fused; the library GEMMs serve grid_pe, no_grid,
+static_mlp and empty_voxel.
 """
 from __future__ import annotations
 
@@ -136,12 +138,16 @@ class Deformation(nn.Module):
             return self.forward_static(rays_pts_emb[:, :3])
         return self.forward_dynamic(rays_pts_emb, scales_emb, rotations_emb, opacity, shs_emb, time_feature, time_emb)
 
-    def _mlp_kernels_fit(self):
-        """What the fused MLP kernels are built for: a plain grid (per-point mask 1), D == 1, W == 64, 128 features, the dshs and
-        feature heads on; no_dx either way."""
+    def _plain_network(self):
+        """What every fused MLP kernel is built for: a plain grid (per-point mask 1), D == 1, W == 64, 128 features."""
         a = self.args
         plain = not (self.no_grid or self.grid_pe != 0 or getattr(a, "static_mlp", False) or getattr(a, "empty_voxel", False))
-        return bool(plain and self.D == 1 and self.W == 64 and self.grid.feat_dim == 128 and not a.no_dshs and a.feat_head)
+        return bool(plain and self.D == 1 and self.W == 64 and self.grid.feat_dim == 128)
+
+    def _mlp_kernels_fit(self):
+        """`_plain_network` with the dshs and feature heads on; no_dx either way."""
+        a = self.args
+        return bool(self._plain_network() and not a.no_dshs and a.feat_head)
 
     def _fused_ok(self):
         """The fused route serves the reference's default heads (dx + dshs + feat) and the static configuration (no_dx: dshs + feat)."""
@@ -155,6 +161,24 @@ class Deformation(nn.Module):
         a = self.args
         return bool(self._mlp_kernels_fit() and not (a.no_ds and a.no_dr and a.no_do))
 
+    def _fused_heads_ok(self):
+        """The fused route WITHOUT the SH head (no_dshs) or without the feature head (feat_head off), the configurations the two older
+        predicates refuse: any subset of dx / ds / dr / do beside them, as long as one of the six heads is on (no_dshs + feat_head off +
+        the geometry heads on is 4D-Gaussian-Splatting's default).  Never true together with `_fused_ok` or `_fused_geometry_ok`, which
+        keep their values."""
+        a = self.args
+        any_head = not (a.no_dx and a.no_ds and a.no_dr and a.no_do and a.no_dshs) or a.feat_head
+        return bool(self._plain_network() and (a.no_dshs or not a.feat_head) and any_head)
+
+    def _fused_any(self):
+        """Any of the three: the configuration runs on the fused kernels."""
+        return self._fused_ok() or self._fused_geometry_ok() or self._fused_heads_ok()
+
+    def _fused_geometry_on(self):
+        """A fused configuration with at least one of the scale / rotation / opacity heads on."""
+        a = self.args
+        return self._fused_any() and not (a.no_ds and a.no_dr and a.no_do)
+
     def _geometry_modules(self):
         """(scales_deform, rotations_deform, opacity_deform) with None for a head the configuration switches off."""
         a = self.args
@@ -167,7 +191,9 @@ class Deformation(nn.Module):
         materialising the [P,16,3] sum.  dx is None for a no_dx network (static scenes): the position head is never evaluated.
         with_geometry=True: one more entry, (ds [P,3], dr [P,4], do [P,1]) -- the outputs of the scale / rotation / opacity heads of a
         `_fused_geometry_ok` network, None for a head that is off -- or None for a network without them; it sits in front of the
-        regulariser's entry."""
+        regulariser's entry.
+        dshs is None for a no_dshs network and feat for one without a feature head (`_fused_heads_ok`); with no chain head at all
+        only the geometry heads run."""
         global infer_cache_hits
         key = None
         if INFER_CACHE and not torch.is_grad_enabled() and reg_weights is None and xyz.is_cuda:
@@ -181,13 +207,14 @@ class Deformation(nn.Module):
             if hit is not None and hit[0] == key and all(t._version == v for t, v in hit[2]):   # (a consumer edited dx in place: miss)
                 infer_cache_hits += 1
                 return self._heads_result(hit[1], with_geometry)
-        need_dx = not self.args.no_dx
-        geometry = self._fused_geometry_ok()
-        if (FUSED_INFERENCE and need_dx and not geometry and not torch.is_grad_enabled() and not need_feat and reg_weights is None and xyz.is_cuda
+        need_dx, need_dshs = not self.args.no_dx, not self.args.no_dshs
+        dino_head = getattr(self, "dino_head", None)        # feat_head off: the module does not exist
+        geometry = self._fused_geometry_on()
+        if (FUSED_INFERENCE and need_dx and need_dshs and not geometry and not torch.is_grad_enabled() and not need_feat and reg_weights is None and xyz.is_cuda
                 and len(self.grid.resolutions) == 4):
             # inference render without the feature image: sampler (+) heads in one kernel, no [P,128] round trip
             dx, dshs = deform_infer(self.grid, xyz[:, :3], time[:, :1], self.feature_out, self.pos_deform, self.shs_deform,
-                                    self.dino_head, uniform_time, arithmetic=INFER_ARITHMETIC)
+                                    dino_head, uniform_time, arithmetic=INFER_ARITHMETIC)
             out = (dx, dshs.reshape([xyz.shape[0], 16, 3]), None)
             if key is not None:
                 self._keep_inference(key, out, xyz, time)
@@ -198,10 +225,10 @@ class Deformation(nn.Module):
         else:
             feats = self.grid(xyz[:, :3], time[:, :1], uniform_time)
         # need_feat=False (honoured only when no backward follows): skip the feature head, `feat` is then None
-        # (a no_dx network's no_grad renders take these two kernels too: the one-kernel route has no variant without the head; so do
-        #  those of a network with geometry heads, which are a third kernel on the same features)
-        dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, self.dino_head, need_feat, need_dx)
-        out = (dx, dshs.reshape([xyz.shape[0], 16, 3]), feat)
+        # (a no_dx or no_dshs network's no_grad renders take these two kernels too: the one-kernel route has no variant without either
+        #  head; so do those of a network with geometry heads, which are a third kernel on the same features)
+        dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, dino_head, need_feat, need_dx, need_dshs)
+        out = (dx, None if dshs is None else dshs.reshape([xyz.shape[0], 16, 3]), feat)
         if geometry:             # the cached evaluation carries ds / dr / do behind the three
             out = out + tuple(geometry_heads(feats, self.feature_out, *self._geometry_modules()))
         if key is not None:      # (no_grad, no regulariser: what an evaluation render with the feature image asks for)
@@ -241,12 +268,15 @@ class Deformation(nn.Module):
 
     def forward_dynamic(self, rays_pts_emb, scales_emb, rotations_emb, opacity_emb, shs_emb, time_feature, time_emb):
         a = self.args
-        geometry = self._fused_geometry_ok()
-        if (geometry or self._fused_ok()) and rays_pts_emb.is_cuda:
-            # reference default configuration: HexPlane sampler -> one fused MFMA MLP kernel (include/s3g_mlp.h)
+        if self._fused_any() and rays_pts_emb.is_cuda:
+            geometry = self._fused_geometry_on()
+            # reference default configuration: HexPlane sampler -> one fused MFMA MLP kernel (include/s3g_mlp.h); a head that is
+            # switched off is skipped in the kernels and comes back as None (no chain head at all: no launch)
             feats = self.grid(rays_pts_emb[:, :3], time_emb[:, :1])
-            dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, self.dino_head, need_dx=not a.no_dx)
-            dshs = dshs.reshape([shs_emb.shape[0], 16, 3])
+            dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, getattr(self, "dino_head", None),
+                                        need_dx=not a.no_dx, need_dshs=not a.no_dshs)
+            if dshs is not None:
+                dshs = dshs.reshape([shs_emb.shape[0], 16, 3])
             pts = rays_pts_emb[:, :3] if dx is None else rays_pts_emb[:, :3] + dx     # no_dx: scene/deformation.py:119-121
             scales, rotations, opacity = scales_emb[:, :3], rotations_emb[:, :4], opacity_emb[:, :1]
             if geometry:
@@ -254,7 +284,7 @@ class Deformation(nn.Module):
                 # mask of scene/deformation.py:108-114 is 1 in every configuration admitted here
                 ds, dr, do = geometry_heads(feats, self.feature_out, *self._geometry_modules())
                 scales, rotations, opacity = self.apply_geometry(scales, rotations, opacity, ds, dr, do)
-            return (pts, scales, rotations, opacity, shs_emb + dshs, dx, feat, dshs)
+            return (pts, scales, rotations, opacity, shs_emb if dshs is None else shs_emb + dshs, dx, feat, dshs)
         # other switch combinations: fused HexPlane sampler + library GEMMs, scene/deformation.py:106-166 line by line
         hidden = self.query_time(rays_pts_emb, scales_emb, rotations_emb, time_feature, time_emb)
         if getattr(a, "static_mlp", False):

@@ -79,12 +79,14 @@ def get_mlp_arithmetic() -> str:
 
 
 _POS = slice(2, 6)     # P1, pb1, P2, pb2: the position head's slots in _NAMES
+_SHS = slice(6, 10)    # S1, sb1, S2, sb2: the SH head's
+_DINO = slice(10, 16)  # D0 .. db2: the feature (dino) head's
 
 
 def _pack(tensors) -> _Params:
     p = _Params()
     for n, shape, t in zip(_NAMES, _SHAPES, tensors):
-        if t is None:      # a gradient slot the library does not touch (the position head's, when it is skipped): NULL
+        if t is None:      # a gradient slot the library does not touch (a skipped head's): NULL
             continue
         if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
             raise RuntimeError(f"deform MLP: parameter {n} must be contiguous float32 {shape}, got {tuple(t.shape)} {t.dtype}")
@@ -92,36 +94,50 @@ def _pack(tensors) -> _Params:
     return p
 
 
+_zero_blocks = {}
+
+
+def _zero_dino(dev):
+    """The six weight slots of a network WITHOUT a dino_head module (feat_head=False): views of one shared block of 4096 zeros per
+    device.  The pack kernels copy whole images whatever the heads, so the slots must point at readable memory."""
+    z = _zero_blocks.get(dev)
+    if z is None:
+        z = _zero_blocks[dev] = torch.zeros(4096, dtype=torch.float32, device=dev)
+    return tuple(z[:int(torch.Size(shape).numel())].view(shape) for shape in _SHAPES[_DINO])
+
+
 class _DeformMLP(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, features, need_feat, grad_mode, pos, *params):
-        # pos is None: `params` are all 16 tensors.  need_dx=False: `params` are the 12 of feature_out / shs_deform / dino_head and
-        # `pos` holds the position head's four, detached and inside a tuple -- NOT inputs of this node (the kernels skip the head but
-        # the pack kernels still copy its weights into the LDS images)
+    def forward(ctx, features, need_feat, grad_mode, fill, *params):
+        # fill is None: `params` are all 16 tensors.  Else `fill` has 16 entries: None for a slot that `params` supplies (in _NAMES order),
+        # a detached tensor for a slot of a head that is skipped -- NOT an input of this node (the kernels skip the head but the pack
+        # kernels still copy its weights into the LDS images): need_dx=False, need_dshs=False, dino_head=None
         if not features.is_cuda:
             raise RuntimeError(f"deform MLP: features must live on the GPU (got {features.device}); no CPU fallback")
         L = _bind()
         x = features.contiguous().float()
         P, dev = x.shape[0], x.device
-        dx = torch.empty((P, 3), dtype=torch.float32, device=dev) if pos is None else None
-        dshs = torch.empty((P, 48), dtype=torch.float32, device=dev)
+        live = lambda sl: fill is None or fill[sl.start] is None
+        has_dino = live(_DINO)
+        dx = torch.empty((P, 3), dtype=torch.float32, device=dev) if live(_POS) else None
+        dshs = torch.empty((P, 48), dtype=torch.float32, device=dev) if live(_SHS) else None
         # needs_input_grad is True for parameters even under torch.no_grad(); the caller's grad mode decides whether a
         # backward can follow (inside Function.forward grad mode is always off)
         need_bwd = bool(grad_mode) and any(ctx.needs_input_grad)
-        need_feat = bool(need_feat) or need_bwd          # the feature head is only skippable when no backward follows
+        need_feat = has_dino and (bool(need_feat) or need_bwd)   # the feature head is only skippable when no backward follows
         feat = torch.empty((P, 3), dtype=torch.float32, device=dev) if need_feat else None
         nbytes = L.s3g_deform_mlp_stash_bytes(P) if need_bwd else L.s3g_deform_mlp_pack_bytes()
         stash = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        w = _pack(_all16(pos, [p.detach() for p in params]))
+        w = _pack(_all16(fill, [p.detach() for p in params]))
+        ptr = lambda t: t.data_ptr() if t is not None else None
         with _lib.on_device(dev):
-            _lib.check(L.s3g_deform_mlp_forward(C.byref(w), P, x.data_ptr(), dx.data_ptr() if dx is not None else None, dshs.data_ptr(),
-                                                feat.data_ptr() if feat is not None else None,
+            _lib.check(L.s3g_deform_mlp_forward(C.byref(w), P, x.data_ptr(), ptr(dx), ptr(dshs), ptr(feat),
                                                 stash.data_ptr(), int(need_bwd), _lib.stream_ptr()))
         if need_bwd:
             ctx.save_for_backward(x, stash, *params)
-            ctx.pos = pos
+            ctx.fill = fill
             ctx.set_materialize_grads(False)   # an output the loss never touched must arrive as None, not as zeros
-        return dx, dshs, feat     # feat is None when the head was skipped (need_feat=False under no_grad)
+        return dx, dshs, feat     # feat is None when the head was skipped (need_feat=False under no_grad) or does not exist
 
     @staticmethod
     def backward(ctx, g_dx, g_dshs, g_feat):
@@ -129,47 +145,56 @@ class _DeformMLP(torch.autograd.Function):
         L = _bind()
         P, dev = x.shape[0], x.device
         z = lambda g, n: (torch.zeros((P, n), dtype=torch.float32, device=dev) if g is None else g.contiguous().float())
-        pos = ctx.pos      # not None: no position head -- NULL for g_dx, no gradient slots for its parameters
-        g_dx, g_dshs = (z(g_dx, 3) if pos is None else None), z(g_dshs, 48)
-        g_dx_ptr = g_dx.data_ptr() if g_dx is not None else None
+        fill = ctx.fill    # a skipped head: NULL for its upstream gradient, no gradient slots for its parameters
+        live = lambda sl: fill is None or fill[sl.start] is None
+        g_dx = z(g_dx, 3) if live(_POS) else None
+        g_dshs = z(g_dshs, 48) if live(_SHS) else None
         # no gradient on the feature output (feature image not in the loss): like the reference, the dino head's parameters
         # then get grad None -- Adam skips them (no moment decay, no step count) -- and its part of the backward is skipped
-        no_feat = g_feat is None
-        g_feat = None if no_feat else g_feat.contiguous().float()
+        # (a node whose ONLY head is the feature head differentiates it against zeros instead: the library needs one head)
+        has_dino = live(_DINO)
+        no_feat = not has_dino or (g_feat is None and (g_dx is not None or g_dshs is not None))
+        g_feat = None if no_feat else z(g_feat, 3)
+        ptr = lambda t: t.data_ptr() if t is not None else None
         gx = torch.empty_like(x)
-        flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)  # one fill, 16 views
+        flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)  # one fill, up to 16 views
         grads, off = [], 0
         for p in params:
             grads.append(flat[off:off + p.numel()].view(p.shape))
             off += p.numel()
         ws = torch.empty((5, P, 64), dtype=torch.float32, device=dev)
-        w, gw = _pack(_all16(pos, [p.detach() for p in params])), _pack(_all16(pos and (None,) * 4, grads))
+        w, gw = _pack(_all16(fill, [p.detach() for p in params])), _pack(_all16(fill, grads, grad_slots=True))
         with _lib.on_device(dev):
             if ORDERED_WGRAD_FLUSH:     # bit-reproducible weight gradients (include/s3g_mlp.h::s3g_deform_mlp_backward_ordered)
                 part = torch.empty(L.s3g_deform_mlp_wgrad_partial_bytes() // 4, dtype=torch.float32, device=dev)
-                _lib.check(L.s3g_deform_mlp_backward_ordered(C.byref(w), P, x.data_ptr(), stash.data_ptr(), g_dx_ptr,
-                                                             g_dshs.data_ptr(), None if no_feat else g_feat.data_ptr(), gx.data_ptr(),
+                _lib.check(L.s3g_deform_mlp_backward_ordered(C.byref(w), P, x.data_ptr(), stash.data_ptr(), ptr(g_dx),
+                                                             ptr(g_dshs), ptr(g_feat), gx.data_ptr(),
                                                              C.byref(gw), ws.data_ptr(), part.data_ptr(), _lib.stream_ptr()))
             else:
-                _lib.check(L.s3g_deform_mlp_backward(C.byref(w), P, x.data_ptr(), stash.data_ptr(), g_dx_ptr,
-                                                     g_dshs.data_ptr(), None if no_feat else g_feat.data_ptr(), gx.data_ptr(),
+                _lib.check(L.s3g_deform_mlp_backward(C.byref(w), P, x.data_ptr(), stash.data_ptr(), ptr(g_dx),
+                                                     ptr(g_dshs), ptr(g_feat), gx.data_ptr(),
                                                      C.byref(gw), ws.data_ptr(), _lib.stream_ptr()))
-        if no_feat:
-            names = _NAMES if pos is None else _NAMES[:_POS.start] + _NAMES[_POS.stop:]
+        if no_feat and has_dino:
+            names = [n for i, n in enumerate(_NAMES) if fill is None or fill[i] is None]
             grads = [None if n.startswith(("D", "db")) else g for n, g in zip(names, grads)]
         return (gx, None, None, None, *grads)
 
 
-def _all16(pos, rest):
-    """The 16 slots of _NAMES from the 12 tensors outside the position head and its 4 (`pos`); pos is None: `rest` already has all 16."""
-    return list(rest) if pos is None else list(rest[:_POS.start]) + list(pos) + list(rest[_POS.start:])
+def _all16(fill, rest, grad_slots=False):
+    """The 16 slots of _NAMES: slot i is fill[i] where that is not None (a skipped head's weight; with grad_slots=True: None, its
+    gradient slot is NULL), else the next tensor of `rest`; fill is None: `rest` already has all 16."""
+    if fill is None:
+        return list(rest)
+    it = iter(rest)
+    return [next(it) if f is None else (None if grad_slots else f) for f in fill]
 
 
 def _head_params(feature_out, pos_deform, shs_deform, dino_head):
+    """The 16 tensors in _NAMES order; the six of a network without a dino_head module (feat_head=False) are None."""
+    dino = [None] * 6 if dino_head is None else [dino_head[0].weight, dino_head[0].bias, dino_head[2].weight, dino_head[2].bias,
+                                                  dino_head[4].weight, dino_head[4].bias]
     return [feature_out[0].weight, feature_out[0].bias, pos_deform[1].weight, pos_deform[1].bias, pos_deform[3].weight,
-            pos_deform[3].bias, shs_deform[1].weight, shs_deform[1].bias, shs_deform[3].weight, shs_deform[3].bias,
-            dino_head[0].weight, dino_head[0].bias, dino_head[2].weight, dino_head[2].bias, dino_head[4].weight,
-            dino_head[4].bias]
+            pos_deform[3].bias, shs_deform[1].weight, shs_deform[1].bias, shs_deform[3].weight, shs_deform[3].bias] + dino
 
 
 @torch.no_grad()
@@ -199,7 +224,10 @@ def deform_infer(grid, xyz, time, feature_out, pos_deform, shs_deform, dino_head
     dx = torch.empty((P, 3), dtype=torch.float32, device=dev)
     dshs = torch.empty((P, 48), dtype=torch.float32, device=dev)
     ws = torch.empty(max(L.s3g_deform_infer_workspace_bytes(C.byref(d)), 4) // 4, dtype=torch.float32, device=dev)
-    w = _pack([p.detach() for p in _head_params(feature_out, pos_deform, shs_deform, dino_head)])
+    ps = _head_params(feature_out, pos_deform, shs_deform, dino_head)
+    if dino_head is None:      # feat_head=False: the kernel never reads the dino slabs' values, the pack kernel copies them
+        ps[_DINO] = _zero_dino(dev)
+    w = _pack([p.detach() for p in ps])
     with _lib.on_device(dev):
         fn = L.s3g_deform_infer_split if arithmetic == "bf16x3" else L.s3g_deform_infer
         _lib.check(fn(C.byref(d), C.byref(w), P, xyz_c.data_ptr(), t_c.data_ptr(), order.data_ptr() if order is not None else None,
@@ -207,15 +235,30 @@ def deform_infer(grid, xyz, time, feature_out, pos_deform, shs_deform, dino_head
     return dx, dshs
 
 
-def deform_mlp(features, feature_out, pos_deform, shs_deform, dino_head, need_feat=True, need_dx=True):
+def deform_mlp(features, feature_out, pos_deform, shs_deform, dino_head, need_feat=True, need_dx=True, need_dshs=True):
     """features [P,128] -> (dx [P,3], dshs [P,48], feat [P,3]) with the reference's Sequential modules as parameter
     holders (feature_out = Sequential(Linear); heads = Sequential(ReLU, Linear, ReLU, Linear); dino = Sequential(Linear,
     ReLU, Linear, ReLU, Linear)).
     need_dx=False (static scenes, ModelHiddenParams no_dx=True): the position head is skipped in every kernel, dx is None, and
     pos_deform's parameters are not inputs of the autograd node -- their .grad stays None, as the reference's autograd leaves it
-    when scene/deformation.py:119-121 never calls the head (Adam then neither decays their moments nor counts a step)."""
+    when scene/deformation.py:119-121 never calls the head (Adam then neither decays their moments nor counts a step).
+    need_dshs=False (no_dshs=True): the same for the SH head -- dshs is None, shs_deform's four parameters are not inputs of the node.
+    These calls run the chain kernels without the SH head (exact fp32 in every arithmetic mode, csrc/mlp_heads.hip).
+    dino_head=None (feat_head=False: the network has no such module): feat is None under autograd too; the library is handed one shared
+    zero block for the head's weight slots and NULL for their gradients.
+    need_feat=False is honoured only when no backward follows.  Nothing to compute -- no dx, no dshs and no feat wanted or possible --
+    means no launch: (None, None, None)."""
     ps = _head_params(feature_out, pos_deform, shs_deform, dino_head)
-    if need_dx:
-        return _DeformMLP.apply(features, need_feat, torch.is_grad_enabled(), None, *ps)
-    pos = tuple(p.detach() for p in ps[_POS])
-    return _DeformMLP.apply(features, need_feat, torch.is_grad_enabled(), pos, *ps[:_POS.start], *ps[_POS.stop:])
+    grad_mode = torch.is_grad_enabled()
+    if need_dx and need_dshs and dino_head is not None:
+        return _DeformMLP.apply(features, need_feat, grad_mode, None, *ps)
+    will_feat = dino_head is not None and (bool(need_feat) or (grad_mode and (features.requires_grad or any(p.requires_grad for p in ps if p is not None))))
+    if not (need_dx or need_dshs or will_feat):
+        return None, None, None
+    fill = [None] * 16
+    for sl, skipped in ((_POS, not need_dx), (_SHS, not need_dshs)):
+        if skipped:
+            fill[sl] = [p.detach() for p in ps[sl]]
+    if dino_head is None:
+        fill[_DINO] = _zero_dino(features.device)
+    return _DeformMLP.apply(features, need_feat, grad_mode, tuple(fill), *(p for p, f in zip(ps, fill) if f is None))

@@ -464,7 +464,7 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
     hy = net.args
     glue_ok = (means3D.is_cuda and override_color is None and getattr(pipe, "convert_SHs_python", True)
                and pc.max_sh_degree == 3 and getattr(pipe, "fused_glue", True))   # pipe.fused_glue=False: torch glue (tests)
-    fused_glue = glue_ok and ("coarse" in stage or net._fused_ok() or net._fused_geometry_ok())
+    fused_glue = glue_ok and ("coarse" in stage or net._fused_any())
     if "coarse" in stage:
         means3D_final, scales_final, rotations_final, opacity_final = means3D, scales, rotations, opacity
         if not fused_glue:
@@ -692,11 +692,25 @@ def _lpips_table(model, n: int, device):
 def _fused_route(pc: GaussianParams, pipe: SimpleNamespace) -> bool:
     """render() takes the fused deformation route for this model AND the model has a position head (a static model, no_dx=True,
     takes the route too, but produces no dx: nothing to colour a flow with or to split dynamic from static by): GPU tensors, the
-    default head configuration (with or without the scale / rotation / opacity heads: Deformation._fused_geometry_ok), SH degree 3,
-    convert_SHs_python and fused_glue on."""
+    plain-grid network with any head configuration that has a position head (Deformation._fused_any: with or without the scale /
+    rotation / opacity, SH and feature heads), SH degree 3, convert_SHs_python and fused_glue on."""
     net = pc._deformation.deformation_net
-    return bool(pc.get_xyz.is_cuda and (net._fused_ok() or net._fused_geometry_ok()) and not net.args.no_dx and pc.max_sh_degree == 3
+    return bool(pc.get_xyz.is_cuda and net._fused_any() and not net.args.no_dx and pc.max_sh_degree == 3
                 and getattr(pipe, "convert_SHs_python", True) and getattr(pipe, "fused_glue", True))
+
+
+def _fused_route_missing(pc: GaussianParams, pipe: SimpleNamespace) -> str:
+    """What `_fused_route` asks for, led by the switch that keeps this model off it."""
+    net = pc._deformation.deformation_net
+    a = net.args
+    if a.no_dx and net._fused_any():
+        lead = "the model was built with no_dx (a static scene): it has no dx to colour a flow with or to split dynamic from static by"
+    else:
+        off = [k for k in ("grid_pe", "no_grid", "static_mlp", "empty_voxel") if getattr(a, k, False)]
+        lead = (f"the switch {' / '.join(off)} puts the network on the library route" if off else
+                "this model or pipe is not on it") + (" (and no_dx is set: a static model has no dx)" if a.no_dx else "")
+    return (lead + ".  Needed: GPU tensors, a plain-grid network (defor_depth 1, net_width 64, 128 grid features) with a position head "
+            "(not no_dx; the other five heads on or off), SH degree 3, convert_SHs_python and fused_glue on")
 
 
 @torch.no_grad()
@@ -729,9 +743,7 @@ def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.T
     net = pc._deformation.deformation_net
     xyz = pc.get_xyz
     if not _fused_route(pc, pipe):
-        raise RuntimeError("render_flows needs the fused deformation route: GPU tensors, the default head configuration "
-                           "(dx + dshs + feature head; not no_dx: a static model has no dx to colour a flow with), SH degree 3, "
-                           "convert_SHs_python and fused_glue on")
+        raise RuntimeError("render_flows needs the fused deformation route: " + _fused_route_missing(pc, pipe))
     dev = xyz.device
     times = [float(cam["time"]) for cam in cameras]
     window: Dict[float, torch.Tensor] = {}      # timestamp -> dx
@@ -798,8 +810,9 @@ def save_split_point_clouds(pc: GaussianParams, time: float, dynamic_pcd_path: s
     if "fine" not in stage:
         raise RuntimeError(f"save_split_point_clouds: stage {stage!r} has no deformation; only the fine stage has a dx")
     xyz = pc.get_xyz
-    if not (xyz.is_cuda and (net._fused_ok() or net._fused_geometry_ok())):
-        raise RuntimeError("save_split_point_clouds needs GPU tensors and the default head configuration (dx + dshs + feature head)")
+    if not (xyz.is_cuda and net._fused_any()):
+        raise RuntimeError("save_split_point_clouds needs GPU tensors and a network on the fused deformation route (plain grid: not "
+                           "grid_pe / no_grid / static_mlp / empty_voxel; defor_depth 1, net_width 64, 128 grid features)")
     dx = net.deform_heads(xyz, _uniform_time(float(time), xyz.device), uniform_time=True, reg_weights=None, need_feat=False)[0]
     return split.export_split(pc, dx, dynamic_pcd_path, static_pcd_path)
 
@@ -849,9 +862,8 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     want_flow = any(k in ("forward_flows", "backward_flows") for k in keys)
     want_dec = any(k in ("dynamic_rgbs", "static_rgbs") for k in keys)
     if (want_flow or want_dec) and not (_fused_route(pc, pipe) and "fine" in stage):
-        raise RuntimeError("evaluate_video: the decomposition and flow keys need the fused deformation route in a fine stage: GPU "
-                           "tensors, the default head configuration (dx + dshs + feature head; not no_dx: a static model has no dx), "
-                           "SH degree 3, convert_SHs_python and fused_glue on")
+        raise RuntimeError("evaluate_video: the decomposition and flow keys need the fused deformation route in a fine stage: "
+                           + _fused_route_missing(pc, pipe))
     if want_flow and stage != "fine":
         raise RuntimeError('evaluate_video: the flow keys are rendered by render_flows, in stage "fine"')
     dev = pc.get_xyz.device
