@@ -121,6 +121,29 @@ int s3g_deform_infer(const s3g_hexplane_desc* d, const s3g_mlp_params* w, int P,
 int s3g_deform_infer_split(const s3g_hexplane_desc* d, const s3g_mlp_params* w, int P, const float* xyz, const float* time,
                            const unsigned int* proc_order, float* dx, float* dshs, void* workspace, void* stream);
 
+/* The one-kernel inference form for the OTHER head sets: sampler (+) feature_out (+) any subset of the position / scale / rotation /
+ * opacity / SH heads whose weight image fits the CU's LDS beside the sampler's staging tiles (csrc/deform_infer_heads.hip).  Exact fp32
+ * only; there is no feature head here.
+ *   head_mask   bit 0 dx, bit 1 ds, bit 2 dr, bit 3 do, bit 4 dshs.
+ *   served      every non-empty subset of {dx, ds, dr, do} with at most three heads (14 sets), dshs alone, dshs with exactly one of
+ *               ds / dr / do (3 sets): 18 sets.  Not served: the empty set, dx + dshs alone (s3g_deform_infer's set) and every set whose
+ *               image does not fit (four first layers beside W0 and the second layers, e.g. all five heads).
+ * s3g_deform_infer_heads_lds_bytes: the dynamic LDS the kernel is launched with for that set (weight image + 8 x 6 912 B of staging; at
+ * most 160 KiB, a multiple of 16), or 0 for a set that is not served.  Pure host code: callable without a GPU.
+ * s3g_deform_infer_heads: xyz [P,3], time [P] -> the outputs whose pointer is not NULL (dx [P,3], dshs [P,48], ds [P,3], dr [P,4],
+ * dopac [P,1]); a NULL output is an absent head, and the weight pointers of an absent head are never read (`gw` may be NULL when none
+ * of ds / dr / dopac is given; feature_out's W0 / b0 are taken from `w`).  Every output is bit-identical to s3g_hexplane_forward ->
+ * s3g_deform_mlp_forward(feat = NULL, save_activations = 0) in S3G_MLP_F32 (without dshs that call is the exact chain in every mode)
+ * -> s3g_deform_geom_forward(save_activations = 0) on the same (xyz, time, proc_order, uniform_time), and what a present head
+ * computes does not depend on which others are present.  The descriptor must have 4 levels; `workspace`:
+ * s3g_deform_infer_workspace_bytes(d) bytes, uninitialised; proc_order as in s3g_hexplane_forward.  P == 0 returns S3G_OK at once
+ * (after the argument checks that need no buffer); a set that is not served returns S3G_ERR_INVALID_ARG with a message naming it. */
+#include "s3g_mlp_geom.h"
+size_t s3g_deform_infer_heads_lds_bytes(int head_mask);
+int s3g_deform_infer_heads(const s3g_hexplane_desc* d, const s3g_mlp_params* w, const s3g_geom_params* gw, int P, const float* xyz,
+                           const float* time, const unsigned int* proc_order, float* dx, float* dshs, float* ds, float* dr,
+                           float* dopac, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

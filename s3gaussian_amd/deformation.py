@@ -12,6 +12,10 @@ With any of no_ds / no_dr / no_do off (scale, rotation, opacity deformation) the
 those heads run as a second fused operator beside the MLP (mlp_geom.geometry_heads, `_fused_geometry_ok`).  So does it with no_dshs on
 or feat_head off (`_fused_heads_ok`): every on/off combination of the six heads runs fused; the library GEMMs serve grid_pe, no_grid,
 static_mlp and empty_voxel.
+Inference (no_grad renders without the feature image) takes ONE kernel, sampler (+) heads with no [P,128] array, for the default heads
+(mlp.deform_infer) and for every other head set whose weights fit the CU's LDS beside the sampler's tiles (mlp.deform_infer_heads,
+`_infer_heads_ok`: static, no_dshs, 4D-Gaussian-Splatting's default, ...); the sets that do not fit (e.g. all five heads) run the
+sampler, the MLP kernel and the geometry-heads kernel one after the other, as training does.
 """
 from __future__ import annotations
 
@@ -23,10 +27,11 @@ import torch.nn.functional as F
 from .hexplane import HexPlaneField
 import os
 
-from .mlp import deform_infer, deform_mlp
+from .mlp import deform_infer, deform_infer_heads, deform_mlp, get_mlp_arithmetic, infer_heads_served
 from .mlp_geom import geometry_heads
 
-# S3G_FUSED_INFERENCE=0: inference renders go through the two separate kernels (sampler, then MLP) like training does
+# S3G_FUSED_INFERENCE=0: inference renders go through the separate kernels (sampler, then MLP, then geometry heads) like training
+# does -- both one-kernel routes (deform_infer, deform_infer_heads) are off
 FUSED_INFERENCE = os.environ.get("S3G_FUSED_INFERENCE", "1") != "0"
 # Arithmetic of the fused inference kernel's GEMM layers: "f32" = exact fp32 fma chains (v_mfma_f32_32x32x2_f32, bit-identical to the
 # training kernels), "bf16x3" = the bf16 matrix pipe on exactly split operands (include/s3g_mlp.h::s3g_deform_infer_split)
@@ -38,6 +43,7 @@ INFER_ARITHMETIC = os.environ.get("S3G_INFER_ARITHMETIC", "bf16x3")
 # timestamp back to back (utils/video_utils.py:116-349 iterates `viewpoint_cams` in dataset order: 3 Waymo cameras per frame)
 INFER_CACHE = os.environ.get("S3G_INFER_CACHE", "1") != "0"
 infer_cache_hits = 0      # renders served from the cache (tests, bench.py)
+_served_sets = {}         # (need_dx, need_dshs, need_ds, need_dr, need_do) -> mlp.infer_heads_served, asked once per set
 
 
 def poc_fre(input_data, poc_buf):
@@ -185,6 +191,23 @@ class Deformation(nn.Module):
         return (None if a.no_ds else self.scales_deform, None if a.no_dr else self.rotations_deform,
                 None if a.no_do else self.opacity_deform)
 
+    def _infer_heads_ok(self):
+        """The one-kernel inference route for the head sets deform_infer does not serve (mlp.deform_infer_heads): a fused network whose
+        set of dx / ds / dr / do / dshs the kernel holds in LDS.  The kernel is the exact fp32 chain.  Without the SH head that is what
+        the separate kernels compute in every arithmetic mode; WITH it they follow mlp.set_mlp_arithmetic, so such a set takes the
+        route only in the "f32" mode, where it changes no bit (in "bf16x3" the separate kernels stay: a render must not depend on the
+        route)."""
+        a = self.args
+        if not self._fused_any():
+            return False
+        if not a.no_dshs and get_mlp_arithmetic() != "f32":
+            return False
+        heads = (not a.no_dx, not a.no_dshs, not a.no_ds, not a.no_dr, not a.no_do)
+        served = _served_sets.get(heads)
+        if served is None:
+            served = _served_sets[heads] = infer_heads_served(*heads)
+        return served
+
     def deform_heads(self, xyz, time, uniform_time=None, reg_weights=None, need_feat=True, with_geometry=False):
         """(dx [P,3], dshs [P,16,3], feat [P,3]) only -- the part of forward_dynamic that is not a pass-through in the
         reference's default configuration.  Lets a caller that fuses `shs + dshs` downstream (pipeline.render) skip
@@ -196,12 +219,15 @@ class Deformation(nn.Module):
         only the geometry heads run."""
         global infer_cache_hits
         key = None
+        # the other one-kernel route: every condition of the first one below, for the head sets mlp.deform_infer_heads serves
+        heads_route = bool(FUSED_INFERENCE and not torch.is_grad_enabled() and not need_feat and reg_weights is None and xyz.is_cuda
+                           and len(self.grid.resolutions) == 4 and self._infer_heads_ok())
         if INFER_CACHE and not torch.is_grad_enabled() and reg_weights is None and xyz.is_cuda:
             # identity + version of everything the outputs depend on (the rasterizer's geometry cache is keyed the same way,
             # raster_C._geom_key): optimizer steps, load_state_dict and in-place edits bump the version counters; writes through
             # `.data` or raw pointers do not -- call raster_C.invalidate_geometry_cache(), which also drops this entry, after those
             key = (tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in (xyz, time)), bool(uniform_time), bool(need_feat),
-                   INFER_ARITHMETIC if not need_feat else "f32", FUSED_INFERENCE,
+                   INFER_ARITHMETIC if not need_feat else "f32", FUSED_INFERENCE, heads_route,
                    tuple((p.data_ptr(), p._version) for p in self.parameters()))
             hit = self.__dict__.get("_infer_cache")
             if hit is not None and hit[0] == key and all(t._version == v for t, v in hit[2]):   # (a consumer edited dx in place: miss)
@@ -219,14 +245,26 @@ class Deformation(nn.Module):
             if key is not None:
                 self._keep_inference(key, out, xyz, time)
             return self._heads_result(out, with_geometry)
+        if heads_route:
+            # the same for a static / no_dshs / geometry-heads network: sampler (+) the heads present in one kernel, bit for bit what
+            # the kernels below compute; the cached evaluation carries ds / dr / do behind the three, as theirs does
+            dx, dshs, ds, dr, do = deform_infer_heads(self.grid, xyz[:, :3], time[:, :1], self.feature_out,
+                                                      self.pos_deform if need_dx else None, self.shs_deform if need_dshs else None,
+                                                      self._geometry_modules() if geometry else (None, None, None), uniform_time)
+            out = (dx, None if dshs is None else dshs.reshape([xyz.shape[0], 16, 3]), None)
+            if geometry:
+                out = out + (ds, dr, do)
+            if key is not None:
+                self._keep_inference(key, out, xyz, time)
+            return self._heads_result(out, with_geometry)
         reg = None
         if reg_weights is not None:   # plane regulariser evaluated on the sampler's autograd node (hexplane_sample)
             feats, reg = self.grid(xyz[:, :3], time[:, :1], uniform_time, reg_weights)
         else:
             feats = self.grid(xyz[:, :3], time[:, :1], uniform_time)
         # need_feat=False (honoured only when no backward follows): skip the feature head, `feat` is then None
-        # (a no_dx or no_dshs network's no_grad renders take these two kernels too: the one-kernel route has no variant without either
-        #  head; so do those of a network with geometry heads, which are a third kernel on the same features)
+        # (so do the no_grad renders of a network whose head set neither one-kernel route serves -- e.g. all five heads, whose weights
+        #  do not fit the LDS beside the sampler's tiles --, with the geometry heads as a third kernel on the same features)
         dx, dshs, feat = deform_mlp(feats, self.feature_out, self.pos_deform, self.shs_deform, dino_head, need_feat, need_dx, need_dshs)
         out = (dx, None if dshs is None else dshs.reshape([xyz.shape[0], 16, 3]), feat)
         if geometry:             # the cached evaluation carries ds / dr / do behind the three

@@ -43,6 +43,11 @@ def _bind():
         L.s3g_deform_infer.argtypes = [C.POINTER(_HexDesc), C.POINTER(_Params), C.c_int, vp, vp, vp, vp, vp, vp, vp]
         L.s3g_deform_infer_split.restype = C.c_int
         L.s3g_deform_infer_split.argtypes = L.s3g_deform_infer.argtypes
+        from .mlp_geom import _GeomParams
+        L.s3g_deform_infer_heads_lds_bytes.restype = C.c_size_t
+        L.s3g_deform_infer_heads_lds_bytes.argtypes = [C.c_int]
+        L.s3g_deform_infer_heads.restype = C.c_int
+        L.s3g_deform_infer_heads.argtypes = [C.POINTER(_HexDesc), C.POINTER(_Params), C.POINTER(_GeomParams), C.c_int] + [vp] * 10
         L.s3g_deform_mlp_set_arithmetic.restype = C.c_int
         L.s3g_deform_mlp_set_arithmetic.argtypes = [C.c_int]
         L.s3g_deform_mlp_get_arithmetic.restype = C.c_int
@@ -233,6 +238,73 @@ def deform_infer(grid, xyz, time, feature_out, pos_deform, shs_deform, dino_head
         _lib.check(fn(C.byref(d), C.byref(w), P, xyz_c.data_ptr(), t_c.data_ptr(), order.data_ptr() if order is not None else None,
                       dx.data_ptr(), dshs.data_ptr(), ws.data_ptr(), _lib.stream_ptr()))
     return dx, dshs
+
+
+_HEAD_BITS = (1, 2, 4, 8, 16)     # dx, ds, dr, do, dshs: the head mask of include/s3g_mlp.h::s3g_deform_infer_heads_lds_bytes
+
+
+def infer_heads_lds_bytes(need_dx, need_dshs, need_ds, need_dr, need_do) -> int:
+    """Dynamic LDS of the one-kernel inference route for this head set, 0 for a set it does not serve (host code: no GPU needed)."""
+    mask = sum(b for b, on in zip(_HEAD_BITS, (need_dx, need_ds, need_dr, need_do, need_dshs)) if on)
+    return int(_bind().s3g_deform_infer_heads_lds_bytes(mask))
+
+
+def infer_heads_served(need_dx, need_dshs, need_ds, need_dr, need_do) -> bool:
+    """Does deform_infer_heads serve this head set?  (Every non-empty subset of dx / ds / dr / do with at most three heads, dshs alone,
+    dshs with one of ds / dr / do; not the empty set, not dx + dshs alone -- deform_infer's -- and no set whose weights do not fit.)"""
+    return infer_heads_lds_bytes(need_dx, need_dshs, need_ds, need_dr, need_do) > 0
+
+
+@torch.no_grad()
+def deform_infer_heads(grid, xyz, time, feature_out, pos_deform, shs_deform, geometry=(None, None, None), uniform_time=None):
+    """Inference only: HexPlane sampler (+) feature_out (+) the heads given, in ONE kernel (include/s3g_mlp.h::s3g_deform_infer_heads).
+    pos_deform / shs_deform / the three entries of geometry = (scales_deform, rotations_deform, opacity_deform): a module given as None
+    is an absent head.  xyz [P,3], time [P,1] -> (dx [P,3], dshs [P,48], ds [P,3], dr [P,4], do [P,1]) with None for absent heads;
+    bit-identical to `deform_mlp(grid(xyz, time), ..., need_feat=False, need_dx=..., need_dshs=...)` (with shs_deform: in the "f32"
+    arithmetic, which is this kernel's only one) and `geometry_heads(grid(xyz, time), ...)` without ever materialising the [P,128]
+    features.  A head set the kernel does not serve (infer_heads_served) is an error, not a fall-back."""
+    from .hexplane import _make_desc
+    from .mlp_geom import _GeomParams
+    if not xyz.is_cuda:
+        raise RuntimeError(f"deform_infer_heads: xyz must live on the GPU (got {xyz.device}); no CPU fallback")
+    L = _bind()
+    P, dev = xyz.shape[0], xyz.device
+    xyz_c = xyz.detach().contiguous().float()
+    t_c = time.detach().reshape(-1).contiguous().float()
+    if t_c.numel() != P and not (uniform_time is True and t_c.numel() == 1):   # uniform time: one shared timestamp is enough
+        raise RuntimeError("time must have one value per point")
+    if uniform_time is None:
+        uniform_time = bool(P > 0 and (t_c == t_c[0]).all().item())
+    d = _make_desc(grid._planes(), grid.resolutions, grid._host_aabb(), bool(uniform_time) and P > 0)
+    order = grid._order_cache.get("order")
+    if order is not None and (order.numel() != P or order.device != dev):
+        order = None
+    heads = (pos_deform, shs_deform) + tuple(geometry)
+    outs = [torch.empty((P, n), dtype=torch.float32, device=dev) if m is not None else None for m, n in zip(heads, (3, 48, 3, 4, 1))]
+    ws = torch.empty(max(L.s3g_deform_infer_workspace_bytes(C.byref(d)), 4) // 4, dtype=torch.float32, device=dev)
+
+    # (host time counts here: a render is a dozen launches long.  Parameters are read where they are -- no detach(), one check each)
+    w, gw = _Params(), _GeomParams()
+    lin = feature_out[0]
+    if tuple(lin.weight.shape) != (64, 128):
+        raise RuntimeError(f"deform_infer_heads: feature_out must be Linear(128, 64), got weight {tuple(lin.weight.shape)}")
+    slots = [(w, "W0", lin.weight), (w, "b0", lin.bias)]
+    for struct, names, m in ((w, ("P1", "pb1", "P2", "pb2"), pos_deform), (w, ("S1", "sb1", "S2", "sb2"), shs_deform),
+                             (gw, ("C1", "cb1", "C2", "cb2"), geometry[0]), (gw, ("R1", "rb1", "R2", "rb2"), geometry[1]),
+                             (gw, ("O1", "ob1", "O2", "ob2"), geometry[2])):
+        if m is not None:      # the four tensors of a present head; an absent head's slots stay NULL (never read)
+            l1, l2 = m[1], m[3]
+            slots += [(struct, names[0], l1.weight), (struct, names[1], l1.bias), (struct, names[2], l2.weight), (struct, names[3], l2.bias)]
+    for struct, n, t in slots:
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise RuntimeError(f"deform_infer_heads: parameter {n} must be a contiguous float32 tensor on {dev}, got {t.dtype} on {t.device}")
+        setattr(struct, n, t.data_ptr())
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with _lib.on_device(dev):
+        _lib.check(L.s3g_deform_infer_heads(C.byref(d), C.byref(w), C.byref(gw), P, xyz_c.data_ptr(), t_c.data_ptr(), ptr(order),
+                                            ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), ptr(outs[4]), ws.data_ptr(),
+                                            _lib.stream_ptr()))
+    return tuple(outs)
 
 
 def deform_mlp(features, feature_out, pos_deform, shs_deform, dino_head, need_feat=True, need_dx=True, need_dshs=True):
