@@ -1,7 +1,7 @@
 """Scale / rotation / opacity deformation (ModelHiddenParams no_ds = no_dr = no_do = False, once more with apply_rotation) on the
 fused deformation route: the module against the reference restatement and against a golden of the reference's own module,
 pipeline.render fused against forced-library, two training steps, and the evaluation entry points.
-"Forced-library" = both route predicates shadowed with `lambda: False` on the module: the library-GEMM branch of forward_dynamic and
+"Forced-library" = tests.util.library_route (`_fused_any = lambda: False` on the module): the library-GEMM branch of forward_dynamic and
 the torch glue, which this configuration took before it was admitted to the fused route.
 The three heads' output layers are re-initialised with std 0.02 (xavier leaves ds / dr / do of order 1, which destroys the scene)."""
 import os
@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from tests.test_static_route_gpu import PIPE, _cam, _model
-from tests.util import rel_l2
+from tests.util import library_route, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -37,20 +37,6 @@ def _geometry_model(scn, hyper, dev, opt=None, seed=0):
     pc = _model(scn, hyper, dev, opt, seed)
     _small_geometry_heads(pc._deformation.deformation_net)
     return pc
-
-
-class _library:
-    """with _library(pc): neither fused route serves the module."""
-
-    def __init__(self, pc):
-        self.net = pc._deformation.deformation_net
-
-    def __enter__(self):
-        self.net._fused_ok = lambda: False
-        self.net._fused_geometry_ok = lambda: False
-
-    def __exit__(self, *exc):
-        del self.net._fused_ok, self.net._fused_geometry_ok          # the instance attributes shadow the methods
 
 
 @pytest.fixture
@@ -162,7 +148,7 @@ def test_geometry_render_fused_and_library_paths_agree(gpu_device, apply_rotatio
         for p in pc.parameters():
             p.grad = None
         if library:
-            with _library(pc):
+            with library_route(pc):
                 pkg = render(cam, pc, pipe, bg, stage="fine", return_dx=True, render_feat=True)
         else:
             pkg = render(cam, pc, pipe, bg, stage="fine", return_dx=True, render_feat=True)
@@ -214,7 +200,7 @@ def test_geometry_training_steps_fused_equal_forced_library(gpu_device):
             if fused:
                 loss, pkg = training_step(pc, cam, *gt, hyper, opt, scn["bg"].to(dev), pipe=pipe, densify_stats=True)
             else:
-                with _library(pc):
+                with library_route(pc):
                     loss, pkg = training_step(pc, cam, *gt, hyper, opt, scn["bg"].to(dev), pipe=pipe, densify_stats=True)
             assert ("dshs_l1" in pkg) == fused and pkg["dx"] is not None and pkg["densify_stats_fused"]
         for head in (net.scales_deform, net.rotations_deform, net.opacity_deform):

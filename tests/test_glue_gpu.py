@@ -1,12 +1,13 @@
 """Fused render glue + full pipeline.render() vs the plain-PyTorch restatement of the reference's glue (pinned to the
 reference by tests/golden/glue.npz): outputs rtol 1e-5, gradients rel-L2 1e-5."""
+import contextlib
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from tests.util import rel_l2
+from tests.util import library_route, rel_l2
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -107,14 +108,8 @@ def test_render_fused_and_unfused_paths_agree(gpu_device):
     def run(force_unfused):
         for p in pc.parameters():
             p.grad = None
-        if force_unfused:
-            real = pc._deformation.deformation_net._fused_ok
-            pc._deformation.deformation_net._fused_ok = lambda: False
-        try:
+        with library_route(pc) if force_unfused else contextlib.nullcontext():
             pkg = render(cam, pc, pipe, bg, stage="fine", return_dx=True, render_feat=True)
-        finally:
-            if force_unfused:
-                pc._deformation.deformation_net._fused_ok = real
         (pkg["render"].sum() + 0.1 * pkg["depth"].sum() + pkg["feat"].sum() + pkg["dx"].abs().sum() + pkg["dshs"].abs().sum()).backward()
         return pkg, {n: p.grad.clone() for n, p in pc.named_parameters() if p.grad is not None}
 

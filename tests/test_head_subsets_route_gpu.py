@@ -1,15 +1,16 @@
 """Networks without the SH head (no_dshs) or without the feature head (feat_head off) on the fused deformation route
 (`Deformation._fused_heads_ok`): the module against the reference restatement, pipeline.render and two training steps fused against
-forced-library, and the evaluation entry points.  "Forced-library" = `_fused_heads_ok = lambda: False` on the module, as
-tests/test_static_route_gpu.py does with `_fused_ok`: the library-GEMM branch these configurations took before they were admitted.
+forced-library, and the evaluation entry points.  "Forced-library" = tests.util.library_route (`_fused_any = lambda: False` on
+the module), as tests/test_static_route_gpu.py forces it: the library-GEMM branch these configurations took before they were admitted.
 Bars: those of tests/test_static_route_gpu.py and tests/test_geometry_route_gpu.py."""
+import contextlib
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from tests.util import rel_l2
+from tests.util import library_route, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -38,19 +39,14 @@ def _cam(scn, i, dev):
     return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in scn["cameras"][i].items()}
 
 
-class _library:
-    """with _library(pc): the module reports that the fused route does not serve it."""
-
-    def __init__(self, pc):
-        self.net = pc._deformation.deformation_net
-
-    def __enter__(self):
-        assert self.net._fused_heads_ok() and not self.net._fused_ok() and not self.net._fused_geometry_ok()
-        self.net._fused_heads_ok = lambda: False
-        assert not self.net._fused_any()
-
-    def __exit__(self, *exc):
-        del self.net._fused_heads_ok          # the instance attribute shadows the method
+@contextlib.contextmanager
+def _library(pc):
+    """with _library(pc): library_route, for a module that only the third family of head switches admits to the fused route."""
+    net = pc._deformation.deformation_net
+    assert net._fused_heads_ok() and not net._fused_ok() and not net._fused_geometry_ok()
+    with library_route(pc):
+        assert not net._fused_any()
+        yield
 
 
 @pytest.fixture(scope="module")

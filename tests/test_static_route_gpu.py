@@ -1,6 +1,6 @@
 """Static scenes (ModelHiddenParams no_dx=True, the reference's arguments/static_nvs.py) on the fused deformation route: the module
 against the reference restatement, pipeline.render fused against forced-unfused, two training steps, the evaluation entry points and
-the zero-edit route.  "Forced-unfused" = `_fused_ok = lambda: False` on the module, as tests/test_glue_gpu.py does: the library-GEMM
+the zero-edit route.  "Forced-unfused" = tests.util.library_route (`_fused_any = lambda: False` on the module): the library-GEMM
 branch this configuration took before it was admitted to the fused route."""
 from types import SimpleNamespace
 
@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import rel_l2
+from tests.util import library_route, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -29,19 +29,6 @@ def _model(scn, hyper, dev, opt=None, seed=0):
 
 def _cam(scn, i, dev):
     return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in scn["cameras"][i].items()}
-
-
-class _unfused:
-    """with _unfused(pc): the module reports that the fused route does not serve it."""
-
-    def __init__(self, pc):
-        self.net = pc._deformation.deformation_net
-
-    def __enter__(self):
-        self.net._fused_ok = lambda: False
-
-    def __exit__(self, *exc):
-        del self.net._fused_ok          # the instance attribute shadows the method
 
 
 def test_static_deformation_module_takes_the_fused_path_and_matches_the_restatement(gpu_device):
@@ -109,7 +96,7 @@ def test_static_render_fused_and_unfused_paths_agree(gpu_device):
         for p in pc.parameters():
             p.grad = None
         if force_unfused:
-            with _unfused(pc):
+            with library_route(pc):
                 pkg = render(cam, pc, pipe, bg, stage="fine", return_dx=True, render_feat=True)
         else:
             pkg = render(cam, pc, pipe, bg, stage="fine", return_dx=True, render_feat=True)
@@ -156,7 +143,7 @@ def test_static_training_steps_fused_equal_forced_unfused(gpu_device):
             if fused:
                 loss, pkg = training_step(pc, cam, *gt, hyper, opt, scn["bg"].to(dev), pipe=pipe, densify_stats=True)
             else:
-                with _unfused(pc):
+                with library_route(pc):
                     loss, pkg = training_step(pc, cam, *gt, hyper, opt, scn["bg"].to(dev), pipe=pipe, densify_stats=True)
             assert ("dshs_l1" in pkg) == fused and pkg["dx"] is None and pkg["densify_stats_fused"]
         for p, p0 in zip(net.pos_deform.parameters(), pos0):

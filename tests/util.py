@@ -1,12 +1,28 @@
 """Shared scene builders / comparison helpers for the tests."""
 from __future__ import annotations
 
+import contextlib
 import math
 
 import numpy as np
 import torch
 
 from s3gaussian_amd import synth
+
+
+@contextlib.contextmanager
+def library_route(pc_or_net):
+    """with library_route(pc): the model's Deformation module (or the module itself) is off the fused route, on the library-GEMM branch
+    of forward_dynamic, whatever family of head switches put it on the fused one.  `_fused_any` is what pipeline.py and
+    forward_dynamic ask, and `_fused_geometry_on` / `_infer_heads_ok` ask it too: shadowing that one method on the instance is enough."""
+    net = pc_or_net._deformation.deformation_net if hasattr(pc_or_net, "_deformation") else pc_or_net
+    assert net._fused_any()
+    net._fused_any = lambda: False
+    try:
+        assert not net._fused_geometry_on() and not net._infer_heads_ok()
+        yield net
+    finally:
+        del net._fused_any          # the instance attribute shadows the method
 
 
 def tiny_scene(P=300, W=48, H=40, seed=0, scale=0.15, sigma=0.4, spread=2.2, bg=(0.2, 0.5, 0.7), zmin=3.0, zmax=6.0):
