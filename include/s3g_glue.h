@@ -36,6 +36,31 @@ int s3g_glue_backward(int P, int deg, const float* f_dc, const float* f_rest, co
                       float* g_xyz, float* g_log_scales, float* g_rot_raw, float* g_opacity_logit,
                       const float* g_dshs_l1, void* stream);
 
+/*
+ *   s3g_glue_forward_views / s3g_glue_backward_views: the same glue for V cameras that share one timestamp -- a batch of
+ *   views (/root/reference/train.py:327-437, opt.batch_size) whose deformation was evaluated once.  1 <= V <= S3G_GLUE_MAX_VIEWS.
+ *   f_dc, f_rest and dshs are read once per Gaussian, the activations are written once, sum|dshs| is taken once.
+ */
+#define S3G_GLUE_MAX_VIEWS 8
+
+/* As s3g_glue_forward with campos [V,3]; colors: HOST array of V device pointers, each [P,3], each written.  A view's colours
+ * are bit-identical to s3g_glue_forward with that view's campos. */
+int s3g_glue_forward_views(int P, int deg, int V, const float* f_dc, const float* f_rest, const float* dshs, const float* xyz,
+                           const float* campos, const float* log_scales, const float* rot_raw, const float* opacity_logit,
+                           float* const* colors, float* scales, float* rot, float* opacity, double* dshs_abs_sum, void* stream);
+
+/* colors: host array of the V forward outputs; g_colors: host array of V upstream gradients [P,3], any entry may be NULL = zero
+ * (the array itself may not).  One each of the other upstream gradients and of every output; all outputs written.
+ *   g_f_dc | g_f_rest | g_dshs row (k, c) = sum_v basis_v[k] * dRGB_v[c]       g_xyz = sum_v (direction term of view v)
+ * both accumulated in fp32, view 0 first, left to right, every product rounded before it is added: the result equals the fp32
+ * sum of V s3g_glue_backward calls, and with V = 1 that call bit for bit.  The g_dshs_l1 term is added after the sum. */
+int s3g_glue_backward_views(int P, int deg, int V, const float* f_dc, const float* f_rest, const float* dshs, const float* xyz,
+                            const float* campos, const float* rot_raw, const float* const* colors, const float* scales,
+                            const float* rot, const float* opacity, const float* const* g_colors, const float* g_scales,
+                            const float* g_rot, const float* g_opacity, float* g_f_dc, float* g_f_rest, float* g_dshs,
+                            float* g_xyz, float* g_log_scales, float* g_rot_raw, float* g_opacity_logit,
+                            const float* g_dshs_l1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

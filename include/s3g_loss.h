@@ -127,6 +127,18 @@ int s3g_photometric_backward(int H, int W, const float* image, const float* gt_i
                              const double* totals, const float* g, float w_ssim, float w_l1, float w_depth, float w_feat,
                              float* g_image, float* g_depth, float* g_feat, void* stream);
 
+/*
+ *   A batch of V views of one H x W (/root/reference/train.py:389-425 on the concatenated [V,3,H,W] tensors) needs no loss kernel
+ *   of its own: s3g_photometric_forward / s3g_pixel_losses_forward ADD into `sums`, so V forward launches into one array hold the
+ *   batch's totals -- [3] is then the JOINT count of valid depth pixels, which is what the reference's mean over the masked
+ *   concatenation divides by.  s3g_pixel_losses_combine_views collapses them like s3g_pixel_losses_combine with
+ *     loss[0] = w_l1 * T1/(n_views N) + w_depth * T2/T3 + w_ssim * (1 - T0/(n_views N)) + w_feat * T4/(n_feat_views N),  N = 3*H*W
+ *   (n_feat_views: how many of the views added a feature pair; the reference supervises the last view's only.  0 needs w_feat == 0).
+ *   The V backward launches then take w_l1 / n_views, w_ssim / n_views, w_feat / n_feat_views and the UNDIVIDED w_depth.
+ */
+int s3g_pixel_losses_combine_views(int H, int W, int n_views, int n_feat_views, const double* sums, double* totals, float w_l1,
+                                   float w_depth, float w_ssim, float w_feat, float* loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

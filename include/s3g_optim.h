@@ -60,6 +60,20 @@ int s3g_densify_stats(int P, const float* grad_xy, int grad_stride, const int* r
 int s3g_densify_stats_guarded(int P, const float* grad_xy, int grad_stride, const int* radii, const unsigned char* visible,
                               float* xyz_gradient_accum, float* denom, float* max_radii2D, const uint32_t* skip_flag, void* stream);
 
+/* The bookkeeping of a BATCH of V views that share one optimizer step (train.py:387-388, 435-437, 489-493), one pass over [P].
+ * grad_xy, radii: HOST arrays of V device pointers ([P, grad_stride] fp32 and [P] int32 each), 1 <= V <= S3G_DENSIFY_MAX_VIEWS.
+ * With g = grad_0 + grad_1 + ... (fp32, left to right), vis = any_v(radii_v > 0) and r = max_v radii_v, where vis holds:
+ *     xyz_gradient_accum[i] += sqrt(gx^2 + gy^2);  denom[i] += 1;  max_radii2D[i] = max(max_radii2D[i], r)
+ * -- what s3g_densify_stats does with (g, r).  The norm is taken of the SUM (the reference sums viewspace_point_tensor.grad
+ * over the batch before add_densification_stats), which is why the rasterizer's fused per-view update cannot serve a batch. */
+#define S3G_DENSIFY_MAX_VIEWS 8
+int s3g_densify_stats_views(int P, int V, const float* const* grad_xy, int grad_stride, const int* const* radii,
+                            float* xyz_gradient_accum, float* denom, float* max_radii2D, void* stream);
+/* skip_flag as in s3g_densify_stats_guarded: the sticky word of the batch's asynchronous forwards. */
+int s3g_densify_stats_views_guarded(int P, int V, const float* const* grad_xy, int grad_stride, const int* const* radii,
+                                    float* xyz_gradient_accum, float* denom, float* max_radii2D, const uint32_t* skip_flag,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

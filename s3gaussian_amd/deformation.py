@@ -43,6 +43,7 @@ INFER_ARITHMETIC = os.environ.get("S3G_INFER_ARITHMETIC", "bf16x3")
 # timestamp back to back (utils/video_utils.py:116-349 iterates `viewpoint_cams` in dataset order: 3 Waymo cameras per frame)
 INFER_CACHE = os.environ.get("S3G_INFER_CACHE", "1") != "0"
 infer_cache_hits = 0      # renders served from the cache (tests, bench.py)
+heads_evaluations = 0     # grad-enabled evaluations of deform_heads: one per training render, one per TIMESTAMP of a pipeline.render_views batch
 _served_sets = {}         # (need_dx, need_dshs, need_ds, need_dr, need_do) -> mlp.infer_heads_served, asked once per set
 
 
@@ -217,7 +218,7 @@ class Deformation(nn.Module):
         regulariser's entry.
         dshs is None for a no_dshs network and feat for one without a feature head (`_fused_heads_ok`); with no chain head at all
         only the geometry heads run."""
-        global infer_cache_hits
+        global infer_cache_hits, heads_evaluations
         key = None
         # the other one-kernel route: every condition of the first one below, for the head sets mlp.deform_infer_heads serves
         heads_route = bool(FUSED_INFERENCE and not torch.is_grad_enabled() and not need_feat and reg_weights is None and xyz.is_cuda
@@ -257,6 +258,8 @@ class Deformation(nn.Module):
             if key is not None:
                 self._keep_inference(key, out, xyz, time)
             return self._heads_result(out, with_geometry)
+        if torch.is_grad_enabled():   # (neither one-kernel route above is taken under autograd)
+            heads_evaluations += 1
         reg = None
         if reg_weights is not None:   # plane regulariser evaluated on the sampler's autograd node (hexplane_sample)
             feats, reg = self.grid(xyz[:, :3], time[:, :1], uniform_time, reg_weights)

@@ -19,6 +19,10 @@ def _bind():
         L.s3g_glue_forward.argtypes = [C.c_int, C.c_int] + [vp] * 14
         L.s3g_glue_backward.restype = C.c_int
         L.s3g_glue_backward.argtypes = [C.c_int, C.c_int] + [vp] * 23
+        L.s3g_glue_forward_views.restype = C.c_int
+        L.s3g_glue_forward_views.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 14
+        L.s3g_glue_backward_views.restype = C.c_int
+        L.s3g_glue_backward_views.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 23
         _bound = True
     return L
 
@@ -88,3 +92,90 @@ def activations_and_colors(deg, f_dc, f_rest, dshs, xyz, campos, log_scales, rot
     with_dshs_l1=True appends mean|dshs| (the train.py:407-410 regulariser, differentiable) computed in the same pass."""
     out = _Glue.apply(deg, f_dc, f_rest, dshs, xyz, campos, log_scales, rot_raw, opacity_logit, with_dshs_l1)
     return out if with_dshs_l1 else out[:4]
+
+
+MAX_VIEWS = 8   # S3G_GLUE_MAX_VIEWS (include/s3g_glue.h)
+
+
+def _ptr_array(tensors):
+    """Host array of device pointers (None -> NULL), as the *_views entry points take them."""
+    return (C.c_void_p * len(tensors))(*[_p(t) for t in tensors])
+
+
+class _GlueViews(torch.autograd.Function):
+    """_Glue for V camera centres of one timestamp: outputs (colors_0 .. colors_{V-1}, scales, rot, opacity, dshs_l1).  Every
+    view's colours are a tensor of their own: the rasterizer of view v hands back the gradient of colors_v and nothing is sliced
+    out of or assembled into a [V,P,3] block."""
+
+    @staticmethod
+    def forward(ctx, deg, f_dc, f_rest, dshs, xyz, campos, log_scales, rot_raw, opacity_logit, want_dshs_l1):
+        if not xyz.is_cuda:
+            raise RuntimeError(f"render glue: tensors must live on the GPU (got {xyz.device}); no CPU fallback")
+        L = _bind()
+        c = lambda t: None if t is None else t.detach().contiguous().float()
+        f_dc, f_rest, dshs, xyz_c, campos_c = c(f_dc), c(f_rest), c(dshs), c(xyz), c(campos)
+        ls, rr, ol = c(log_scales), c(rot_raw), c(opacity_logit)
+        P, dev, V = xyz_c.shape[0], xyz_c.device, campos_c.shape[0]
+        if f_dc.shape != (P, 1, 3) or f_rest.shape != (P, 15, 3):
+            raise RuntimeError("render glue expects f_dc [P,1,3] and f_rest [P,15,3] (sh_degree 3 storage)")
+        colors = [torch.empty((P, 3), dtype=torch.float32, device=dev) for _ in range(V)]
+        scales = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        rot = torch.empty((P, 4), dtype=torch.float32, device=dev)
+        opac = torch.empty((P, 1), dtype=torch.float32, device=dev)
+        asked_l1 = bool(want_dshs_l1)
+        want_dshs_l1 = asked_l1 and dshs is not None and P > 0
+        abs_sum = torch.zeros(64 * 16, dtype=torch.float64, device=dev) if want_dshs_l1 else None   # S3G_SUM_DOUBLES
+        with _lib.on_device(dev):
+            _lib.check(L.s3g_glue_forward_views(P, int(deg), V, _p(f_dc), _p(f_rest), _p(dshs), _p(xyz_c), _p(campos_c), _p(ls),
+                                                _p(rr), _p(ol), _ptr_array(colors), _p(scales), _p(rot), _p(opac), _p(abs_sum),
+                                                _lib.stream_ptr()))
+        ctx.deg, ctx.V = int(deg), V
+        ctx.has_dshs = dshs is not None
+        ctx.save_for_backward(f_dc, f_rest, dshs if dshs is not None else torch.empty(0, device=dev), xyz_c, campos_c, rr,
+                              scales, rot, opac, *colors)
+        ctx.want_dshs_l1 = want_dshs_l1
+        ctx.set_materialize_grads(False)     # a view whose colours fed nothing passes NULL instead of a [P,3] block of zeros
+        if want_dshs_l1:
+            dshs_l1 = (abs_sum.sum() / (48.0 * P)).float()
+        elif asked_l1:
+            dshs_l1 = torch.zeros((), dtype=torch.float32, device=dev)     # asked for, nothing to sum (no dshs / P == 0)
+        else:
+            dshs_l1 = torch.empty((), dtype=torch.float32, device=dev)     # not asked for: dropped by the wrapper, no fill launch
+        return (*colors, scales, rot, opac, dshs_l1)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        V = ctx.V
+        f_dc, f_rest, dshs, xyz, campos, rr, scales, rot, opac, *colors = ctx.saved_tensors
+        L = _bind()
+        P, dev = xyz.shape[0], xyz.device
+        dshs = dshs if ctx.has_dshs else None
+        c = lambda t: None if t is None else t.contiguous().float()
+        g_colors = [c(g) for g in grads[:V]]
+        g_scales, g_rot, g_opac, g_l1 = (c(g) for g in grads[V:V + 4])
+        e = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        g_f_dc, g_f_rest, g_xyz, g_ls, g_rr, g_ol = e(P, 1, 3), e(P, 15, 3), e(P, 3), e(P, 3), e(P, 4), e(P, 1)
+        g_dshs = e(P, 16, 3) if ctx.has_dshs else None
+        g_l1 = g_l1 if ctx.want_dshs_l1 else None
+        with _lib.on_device(dev):
+            _lib.check(L.s3g_glue_backward_views(P, ctx.deg, V, _p(f_dc), _p(f_rest), _p(dshs), _p(xyz), _p(campos), _p(rr),
+                                                 _ptr_array(colors), _p(scales), _p(rot), _p(opac), _ptr_array(g_colors),
+                                                 _p(g_scales), _p(g_rot), _p(g_opac), _p(g_f_dc), _p(g_f_rest), _p(g_dshs),
+                                                 _p(g_xyz), _p(g_ls), _p(g_rr), _p(g_ol), _p(g_l1), _lib.stream_ptr()))
+        return None, g_f_dc, g_f_rest, g_dshs, g_xyz, None, g_ls, g_rr, g_ol, None
+
+
+def activations_and_colors_views(deg, f_dc, f_rest, dshs, xyz, campos_list, log_scales, rot_raw, opacity_logit,
+                                 with_dshs_l1=False):
+    """activations_and_colors for the V cameras of one timestamp (1 <= V <= 8) in one pass each way
+    (include/s3g_glue.h::s3g_glue_*_views): -> ([colors_0 .. colors_{V-1}], scales, rotations, opacity[, dshs_l1]).
+    campos_list: V camera centres ([3] each) or one [V,3] tensor.  Colours are bit-identical to V single-camera calls; the
+    gradients are their fp32 sum, view 0 first."""
+    campos = campos_list if torch.is_tensor(campos_list) else torch.stack([torch.as_tensor(cp).reshape(3) for cp in campos_list])
+    campos = campos.reshape(-1, 3)
+    V = campos.shape[0]
+    if not 1 <= V <= MAX_VIEWS:
+        raise RuntimeError(f"render glue: {V} views in one call (1 .. {MAX_VIEWS} are served)")
+    out = _GlueViews.apply(deg, f_dc, f_rest, dshs, xyz, campos.to(xyz.device), log_scales, rot_raw, opacity_logit, with_dshs_l1)
+    res = (list(out[:V]), out[V], out[V + 1], out[V + 2])
+    return res + (out[V + 3],) if with_dshs_l1 else res

@@ -170,6 +170,123 @@ def photometric_loss(image, gt_image, depth=None, gt_depth=None, feat=None, gt_f
                                   max_depth)
 
 
+class _PhotometricLossViews(torch.autograd.Function):
+    """_PhotometricLoss over the concatenated batch of V views of one H x W (train.py:389-425): V forward launches ADD into one
+    set of accumulators, one combine (include/s3g_loss.h::s3g_pixel_losses_combine_views), V backward launches.  L1 and SSIM are
+    means over V*3*H*W, the depth term over the batch's joint count of valid pixels, the feature term over the views that have one."""
+
+    @staticmethod
+    def forward(ctx, V, w_ssim, w_depth, w_feat, max_depth, *flat):
+        images, gts, depths, gt_depths, feats, gt_feats = (list(flat[k * V:(k + 1) * V]) for k in range(6))
+        if not images[0].is_cuda:
+            raise RuntimeError(f"photometric_loss_views: images must live on the GPU (got {images[0].device}); no CPU fallback")
+        L = _bind()
+        L.s3g_pixel_losses_combine_views.restype = C.c_int
+        L.s3g_pixel_losses_combine_views.argtypes = ([C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_float] * 4 + [C.c_void_p] * 2)
+        c = lambda t: None if t is None else t.detach().contiguous().float()
+        w_ssim, w_depth, w_feat, max_depth = float(w_ssim), float(w_depth), float(w_feat), float(max_depth)
+        _, H, W = images[0].shape
+        dev = images[0].device
+        views = []
+        for v in range(V):
+            img, gt = c(images[v]), c(gts[v])
+            if img.dim() != 3 or img.shape[0] != 3 or gt.shape != img.shape:
+                raise RuntimeError(f"photometric_loss_views: view {v}: image and gt_image must be [3,H,W] (got {tuple(img.shape)}, "
+                                   f"{tuple(gt.shape)})")
+            if tuple(img.shape[1:]) != (H, W):
+                raise RuntimeError(f"photometric_loss_views: view {v} is {img.shape[1]}x{img.shape[2]}, view 0 is {H}x{W}: "
+                                   "all views of a batch must have one size")
+            dep, gdep = (c(depths[v]), c(gt_depths[v])) if (depths[v] is not None and w_depth != 0.0) else (None, None)
+            ft, gft = (c(feats[v]), c(gt_feats[v])) if (feats[v] is not None and w_feat != 0.0) else (None, None)
+            for a, b, n in ((dep, gdep, H * W), (ft, gft, 3 * H * W)):
+                if a is not None and (b is None or a.numel() != n or b.numel() != n):
+                    raise RuntimeError(f"photometric_loss_views: view {v}: depth must have H*W and feat 3*H*W elements, like "
+                                       "their targets")
+            views.append((img, gt, dep, gdep, ft, gft))
+        n_feat = sum(1 for vw in views if vw[4] is not None)
+        any_depth = any(vw[2] is not None for vw in views)
+        sums = torch.zeros(5 * SUM_DOUBLES + 5, dtype=torch.float64, device=dev)   # 5 accumulators + their 5 totals
+        totals = sums[5 * SUM_DOUBLES:]
+        maps = [_new_maps((3, 3, H, W), dtype=torch.float32, device=dev) for _ in range(V)] if w_ssim != 0.0 else None
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        p = lambda t: None if t is None else t.data_ptr()
+        with _lib.on_device(dev):
+            st = _lib.stream_ptr()
+            for v, (img, gt, dep, gdep, ft, gft) in enumerate(views):
+                if maps is not None:
+                    m = maps[v]
+                    _lib.check(L.s3g_photometric_forward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(sums),
+                                                         p(m[0]), p(m[1]), p(m[2]), st))
+                else:
+                    _lib.check(L.s3g_pixel_losses_forward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth,
+                                                          p(sums), st))
+            _lib.check(L.s3g_pixel_losses_combine_views(H, W, V, n_feat, p(sums), p(totals), 1.0, w_depth if any_depth else 0.0,
+                                                        w_ssim, w_feat if n_feat else 0.0, p(loss), st))
+        ctx.save_for_backward(*(t for vw in views for t in vw if t is not None), *(maps or ()), totals)
+        ctx.present = [[t is not None for t in vw] for vw in views]
+        ctx.cfg = (V, H, W, n_feat, w_ssim, w_depth, w_feat, max_depth)
+        ctx.shapes = [tuple(None if t is None else t.shape for t in (images[v], depths[v], feats[v])) for v in range(V)]
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        V, H, W, n_feat, w_ssim, w_depth, w_feat, max_depth = ctx.cfg
+        L = _bind()
+        saved = iter(ctx.saved_tensors)
+        views = [tuple(next(saved) if there else None for there in row) for row in ctx.present]
+        maps = [next(saved) for _ in range(V)] if w_ssim != 0.0 else None
+        totals = next(saved)
+        g = g.detach().reshape(1).contiguous().float()
+        # the kernels divide by this view's 3*H*W: the batch means take 1/V (1/n_feat) more.  The depth weight stays whole:
+        # totals[3], which the kernels divide by, already is the joint count
+        w_l1_v, w_ssim_v, w_feat_v = 1.0 / V, w_ssim / V, (w_feat / n_feat if n_feat else 0.0)
+        p = lambda t: None if t is None else t.data_ptr()
+        g_imgs, g_deps, g_fts = [], [], []
+        with _lib.on_device(totals.device):
+            st = _lib.stream_ptr()
+            for v, (img, gt, dep, gdep, ft, gft) in enumerate(views):
+                g_img = _new_grad(img)
+                g_dep = _new_grad(dep) if dep is not None else None
+                g_ft = _new_grad(ft) if ft is not None else None
+                if maps is not None:
+                    m = maps[v]
+                    _lib.check(L.s3g_photometric_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(m[0]),
+                                                          p(m[1]), p(m[2]), p(totals), p(g), w_ssim_v, w_l1_v, w_depth, w_feat_v,
+                                                          p(g_img), p(g_dep), p(g_ft), st))
+                else:
+                    _lib.check(L.s3g_pixel_losses_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(totals),
+                                                           p(g), w_l1_v, w_depth, w_feat_v, p(g_img), 0, p(g_dep), p(g_ft), st))
+                ishape, dshape, fshape = ctx.shapes[v]
+                g_imgs.append(g_img.view(ishape))
+                g_deps.append(None if g_dep is None else g_dep.view(dshape))
+                g_fts.append(None if g_ft is None else g_ft.view(fshape))
+        none = [None] * V
+        return (None, None, None, None, None, *g_imgs, *none, *g_deps, *none, *g_fts, *none)
+
+
+def photometric_loss_views(images, gt_images, depths=None, gt_depths=None, feats=None, gt_feats=None, lambda_dssim=0.0,
+                           lambda_depth=0.0, lambda_feat=0.0, max_depth=80.0):
+    """photometric_loss for a batch of V views of one H x W, with the reference's batch semantics (train.py:389-425 on the
+    concatenated tensors), as ONE autograd node:
+        l1_loss(cat(images), cat(gt_images)) + lambda_depth * compute_depth("l2", cat(depths), cat(gt_depths))
+        + lambda_dssim * (1 - ssim(cat(images), cat(gt_images))) + lambda_feat * l2_loss(cat(feats'), cat(gt_feats'))
+    L1 and SSIM are means over V*3*H*W elements; the depth term is the mean over the valid pixels of the WHOLE batch (one joint
+    count, not the mean of per-view means); feats / gt_feats are lists with None for a view whose feature image is not
+    supervised (the reference supervises the last view's only), the mean is over the views that have one."""
+    V = len(images)
+    if V < 1:
+        raise RuntimeError("photometric_loss_views: no views")
+    none = [None] * V
+    lists = [list(images), list(gt_images), list(depths) if depths is not None else none,
+             list(gt_depths) if gt_depths is not None else none, list(feats) if feats is not None else none,
+             list(gt_feats) if gt_feats is not None else none]
+    for name, l in zip(("images", "gt_images", "depths", "gt_depths", "feats", "gt_feats"), lists):
+        if len(l) != V:
+            raise RuntimeError(f"photometric_loss_views: {name} has {len(l)} entries for {V} views")
+    flat = [t for l in lists for t in l]
+    return _PhotometricLossViews.apply(V, lambda_dssim, lambda_depth, lambda_feat, max_depth, *flat)
+
+
 class _PixelTerms(torch.autograd.Function):
     """w_l1 * l1(image, gt) + w_depth * depth_l2(depth, gt_depth) + w_feat * l2(feat, gt_feat) with any subset of the three
     pairs present: one kernel forward (+ the 64-lane combine), one backward (include/s3g_loss.h::s3g_pixel_losses_*).  The

@@ -232,3 +232,42 @@ def densify_stats(xyz_gradient_accum: torch.Tensor, denom: torch.Tensor, max_rad
                                                _lib.stream_ptr()))
     for t_ in (xyz_gradient_accum, denom, max_radii2D):
         torch.autograd.graph.increment_version(t_)
+
+
+@torch.no_grad()
+def densify_stats_views(xyz_gradient_accum: torch.Tensor, denom: torch.Tensor, max_radii2D: torch.Tensor,
+                        viewspace_grads, radii_list) -> None:
+    """densify_stats for a batch of V views that share one optimizer step (train.py:387-388, 435-437, 489-493;
+    include/s3g_optim.h::s3g_densify_stats_views): the viewspace gradients are summed (left to right) BEFORE the norm, a
+    Gaussian counts once if any view saw it (radii > 0), the radius is the largest of the views'.  One pass over [P]."""
+    L = _lib.lib()
+    vp = C.c_void_p
+    L.s3g_densify_stats_views_guarded.restype = C.c_int
+    L.s3g_densify_stats_views_guarded.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    V = len(radii_list)
+    if not 1 <= V <= 8 or len(viewspace_grads) != V:      # S3G_DENSIFY_MAX_VIEWS
+        raise RuntimeError(f"densify_stats_views: {len(viewspace_grads)} gradients and {V} radii (1 .. 8 views, one of each per view)")
+    P, dev = radii_list[0].shape[0], radii_list[0].device
+    for name, t_ in (("xyz_gradient_accum", xyz_gradient_accum), ("denom", denom), ("max_radii2D", max_radii2D)):
+        if not (t_.is_cuda and t_.dtype == torch.float32 and t_.is_contiguous() and t_.numel() == P):
+            raise RuntimeError(f"densify_stats_views: {name} must be a contiguous float32 GPU tensor with {P} elements")
+    gs, rs = [], []
+    for v, (g, r) in enumerate(zip(viewspace_grads, radii_list)):
+        if not (g.is_cuda and r.is_cuda) or g.dim() != 2 or g.shape[0] != P or g.shape[1] < 2 or r.shape[0] != P:
+            raise RuntimeError(f"densify_stats_views: view {v}: the gradient must be a GPU tensor [P,>=2] and the radii [P], P = {P} "
+                               f"(got {g.device} {tuple(g.shape)}, {r.device} {tuple(r.shape)})")
+        gs.append(g.float().contiguous())      # no-ops for what the rasterizer hands back
+        rs.append(r.to(torch.int32).contiguous())
+    stride = int(gs[0].shape[1])
+    if any(int(g.shape[1]) != stride for g in gs):
+        raise RuntimeError("densify_stats_views: the views' gradients must have one width")
+    from . import raster_C
+    flag = raster_C.async_skip_flag(dev)     # sticky over the batch's forwards: one overflowed view drops the batch's statistics
+    ga = (vp * V)(*[g.data_ptr() for g in gs])
+    ra = (vp * V)(*[r.data_ptr() for r in rs])
+    with _lib.on_device(dev):
+        _lib.check(L.s3g_densify_stats_views_guarded(P, V, ga, stride, ra, xyz_gradient_accum.data_ptr(), denom.data_ptr(),
+                                                     max_radii2D.data_ptr(), flag.data_ptr() if flag is not None else None,
+                                                     _lib.stream_ptr()))
+    for t_ in (xyz_gradient_accum, denom, max_radii2D):
+        torch.autograd.graph.increment_version(t_)

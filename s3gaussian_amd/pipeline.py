@@ -4,6 +4,10 @@
   render()            <- gaussian_renderer/__init__.py:23-210 (same arguments, same result-dict keys)
   training_loss()     <- train.py:395-425 loss assembly (L1 + dx/dshs reg + depth L2 + plane regulation + DSSIM + feat L2)
   training_step()     <- train.py:372-437,521-522 for one view (batch_size = 1)
+  render_views(), training_loss_views(), training_step_views()
+                      <- the same for a batch of views (opt.batch_size, train.py:286, 327-437): one deformation pass and one glue
+                         pass per TIMESTAMP of the batch, one loss node, one backward, one Adam step; rig_batches() groups a rig's
+                         cameras by timestamp
   evaluate()          <- the metric part of utils/video_utils.py:169-241 (PSNR, SSIM and their masked forms per frame, metrics.py)
   render_flows()      <- the flow part of utils/video_utils.py:203-209, 252-299 (forward / backward scene-flow images, flow.py)
   evaluate_video()    <- utils/video_utils.py:116-349 + 439-499 in one pass: metrics, decomposition, flows and the uint8 strips the
@@ -1078,6 +1082,239 @@ def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hy
         pc.optimizer.step()
     pc.optimizer.zero_grad(set_to_none=True)
     return loss.detach(), pkg
+
+
+# ---- a batch of views per iteration (train.py:286, 327-437: opt.batch_size) ----------------------------------------------------------
+def rig_batches(cameras, num_cams: int = 3):
+    """Index lists, one per timestamp: consecutive cameras with one `time`, at most `num_cams` each (a rig delivers its cameras of a
+    frame back to back, as evaluate_video's strips assume).  What a caller samples from to feed training_step_views batches that
+    share one deformation pass; which batch comes when stays with the caller."""
+    n = int(num_cams)
+    if n < 1:
+        raise RuntimeError(f"rig_batches: num_cams = {num_cams}")
+    out = []
+    for i, cam in enumerate(cameras):
+        t = float(cam["time"])
+        if out and len(out[-1]) < n and float(cameras[out[-1][0]]["time"]) == t:
+            out[-1].append(i)
+        else:
+            out.append([i])
+    return out
+
+
+def _views_on_fused_route(pc: GaussianParams, pipe: SimpleNamespace, stage: str) -> bool:
+    """render()'s own condition for the fused glue (+ fused deformation) route, for the models render_views serves in one pass."""
+    net = pc._deformation.deformation_net
+    return bool(pc.get_xyz.is_cuda and getattr(pipe, "convert_SHs_python", True) and pc.max_sh_degree == 3
+                and getattr(pipe, "fused_glue", True) and not getattr(pipe, "compute_cov3D_python", False)
+                and ("coarse" in stage or net._fused_any()))
+
+
+def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation):
+    """-> (result dicts, the skip word of each view's asynchronous forward or None)."""
+    from . import raster_C
+    from .glue import MAX_VIEWS, activations_and_colors_views
+    V = len(cams)
+    flags = [bool(render_feat)] * V if isinstance(render_feat, (bool, int)) else [bool(f) for f in render_feat]
+    if len(flags) != V:
+        raise RuntimeError(f"render_views: render_feat has {len(flags)} entries for {V} views")
+    if "coarse" not in stage and "fine" not in stage:
+        raise NotImplementedError
+    dev = pc.get_xyz.device
+    if not _views_on_fused_route(pc, pipe, stage):
+        outs, words = [], []
+        for cam, f in zip(cams, flags):     # the library route: nothing to share, the same results contract
+            outs.append(render(cam, pc, pipe, bg_color, stage=stage, return_dx=return_dx, render_feat=f))
+            words.append(raster_C.async_skip_flag(dev) if dev.type == "cuda" else None)
+        return outs, words
+    groups: Dict[float, list] = {}
+    for i, cam in enumerate(cams):
+        groups.setdefault(float(cam["time"]) if share_deformation else i, []).append(i)
+    chunks = [idx[k:k + MAX_VIEWS] for idx in groups.values() for k in range(0, len(idx), MAX_VIEWS)]
+    net = pc._deformation.deformation_net
+    hy = net.args
+    grad = torch.is_grad_enabled()
+    outs, words = [None] * V, [None] * V
+    for gi, idx in enumerate(chunks):
+        means3D = pc.get_xyz
+        scales, rotations, opacity = pc._scaling, pc._rotation, pc._opacity
+        dx = feat = dshs = plane_reg = None
+        if "coarse" in stage:
+            means3D_final = means3D
+        else:
+            # ONE evaluation of the field for the views of this timestamp; the plane regulariser is a term of the iteration, not of
+            # a view: it rides on the first group's sampler node only
+            regw = ((hy.time_smoothness_weight, hy.l1_time_planes, hy.plane_tv_weight)
+                    if (gi == 0 and stage == "fine" and grad and hy.time_smoothness_weight != 0) else None)
+            heads = net.deform_heads(means3D, _uniform_time(float(cams[idx[0]]["time"]), dev), uniform_time=True, reg_weights=regw,
+                                     need_feat=any(flags[i] for i in idx) or grad, with_geometry=True)
+            dx, dshs, feat = heads[:3]
+            plane_reg = heads[4] if regw is not None else None
+            means3D_final = means3D if dx is None else means3D + dx
+            if heads[3] is not None:
+                scales, rotations, opacity = net.apply_geometry(scales, rotations, opacity, *heads[3])
+        want_l1 = dshs is not None and grad
+        glue_out = activations_and_colors_views(pc.active_sh_degree, pc._features_dc, pc._features_rest, dshs, pc.get_xyz,
+                                                torch.stack([cams[i]["campos"].reshape(3) for i in idx]), scales, rotations, opacity,
+                                                with_dshs_l1=want_l1)
+        colors, scales_final, rotations_final, opacity_final = glue_out[:4]
+        dshs_l1 = glue_out[4] if want_l1 else None
+        for k, i in enumerate(idx):
+            cam = cams[i]
+            rs = GaussianRasterizationSettings(
+                image_height=int(cam["image_height"]), image_width=int(cam["image_width"]), tanfovx=cam["tanfovx"],
+                tanfovy=cam["tanfovy"], bg=bg_color, scale_modifier=1.0, viewmatrix=cam["viewmatrix"],
+                projmatrix=cam["projmatrix"], sh_degree=pc.active_sh_degree, campos=cam["campos"], prefiltered=False,
+                debug=getattr(pipe, "debug", False))
+            rasterizer = GaussianRasterizer(raster_settings=rs)
+            means2D = torch.empty_like(pc.get_xyz).requires_grad_(True)      # carries the viewspace gradient of THIS view (see render)
+            want_feat = flags[i] and "fine" in stage
+            # densify_accum is never handed over: a batch's statistics take the norm of the SUMMED viewspace gradient
+            if want_feat and getattr(pipe, "fused_pair", True):
+                image, radii, depth, image2 = rasterizer.forward_pair(
+                    means3D=means3D_final, means2D=means2D, opacities=opacity_final, colors_a=colors[k], colors_b=feat,
+                    scales=scales_final, rotations=rotations_final, cov3D_precomp=None, densify_accum=None)
+            else:
+                image, radii, depth = rasterizer(means3D=means3D_final, means2D=means2D, shs=None, colors_precomp=colors[k],
+                                                 opacities=opacity_final, scales=scales_final, rotations=rotations_final,
+                                                 cov3D_precomp=None)
+                if want_feat:
+                    image2, _, _ = rasterizer(means3D=means3D_final, means2D=means2D, shs=None, colors_precomp=feat,
+                                              opacities=opacity_final, scales=scales_final, rotations=rotations_final,
+                                              cov3D_precomp=None)
+            words[i] = raster_C.async_skip_flag(dev)
+            out = _LazyResult({"render": image, "viewspace_points": means2D, "visibility_filter": radii > 0, "radii": radii,
+                               "depth": depth})
+            if want_feat:
+                out["feat"] = image2
+            if return_dx and "fine" in stage:
+                out.update({"dx": dx, "dshs": dshs})
+                if dshs_l1 is not None:
+                    out["dshs_l1"] = dshs_l1
+            if plane_reg is not None:
+                out["plane_reg"] = plane_reg
+            outs[i] = out
+    return outs, words
+
+
+def render_views(cams, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torch.Tensor, stage="fine", render_feat=False,
+                 return_dx=True, share_deformation=True):
+    """render() for a batch of views -> a list of result dicts with the keys render() returns, in the order of `cams`.
+    The deformation field depends on (xyz, t) only, never on the camera.  On the fused route (stage "coarse", or a network on
+    Deformation._fused_any with the fused glue: every head subset, no_dx, the geometry heads) the views are grouped by cam["time"]
+    and each distinct timestamp gets ONE deform_heads evaluation and ONE glue pass for all its cameras
+    (glue.activations_and_colors_views; more than 8 cameras of one timestamp are served in chunks of 8, each chunk with passes of
+    its own); only the rasterizer runs per view
+    (forward_pair where the view's feature image is wanted, the plain rasterizer otherwise).  The tensors of one timestamp --
+    "dx", "dshs", "dshs_l1" -- are shared by its views' dicts; "plane_reg" (the HexPlane regulariser, under autograd in stage
+    "fine") appears in the first timestamp's dicts only: it is a term of the iteration, not of a view.
+    render_feat: a bool, or one bool per view.  share_deformation=False: one evaluation per view (A/B measurements, equivalence
+    tests).  On the library route (grid_pe, no_grid, static_mlp, empty_voxel, pipe.fused_glue=False, convert_SHs_python=False,
+    compute_cov3D_python) this is one render() per view: same contract, nothing shared.
+    No densify_accum here: a batch's densification statistics take the norm of the summed viewspace gradient
+    (optim.densify_stats_views), which a per-view update inside the rasterizer's backward cannot give."""
+    return _render_views(list(cams), pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation)[0]
+
+
+def _supervised_feat_views(V: int, hyper, stage: str, feat_views: str):
+    if feat_views not in ("last", "all"):
+        raise RuntimeError(f'feat_views must be "last" (the reference) or "all", got {feat_views!r}')
+    use_feat = stage == "fine" and hyper.feat_head
+    return [bool(use_feat and (feat_views == "all" or v == V - 1)) for v in range(V)]
+
+
+def training_loss_views(pc: GaussianParams, pkgs, gt_images, gt_depths, gt_feats, hyper, opt, stage="fine", feat_views="last"):
+    """train.py:389-425 for a batch of V views, the reference's semantics line for line, quirks included:
+      - L1 and SSIM are means over all V*3*H*W elements of the concatenated images;
+      - the depth term is the mean over the valid pixels of the WHOLE batch (one joint count, not a mean of per-view means);
+      - lambda_dx * mean|dx|, lambda_dshs * mean|dshs| and lambda_feat * l2(feat, gt_feat) come from the LAST view's package only
+        (the reference reads `render_pkg` after its loop);
+      - the plane regulariser is applied once.
+    feat_views="all" (an extension for rigs whose every camera has a feature map, NOT the reference's behaviour) supervises every
+    view's feature image instead: the mean over V*3*H*W.  One fused node for the per-pixel terms (losses.photometric_loss_views)."""
+    from .losses import photometric_loss_views
+    V = len(pkgs)
+    if V < 1 or len(gt_images) != V:
+        raise RuntimeError(f"training_loss_views: {V} views, {len(gt_images)} ground-truth images")
+    sup = _supervised_feat_views(V, hyper, stage, feat_views)
+    H, W = pkgs[0]["render"].shape[-2:]
+    for v, p in enumerate(pkgs):
+        h, w = p["render"].shape[-2:]
+        if (h, w) != (H, W):
+            raise RuntimeError(f"training_loss_views: view {v} renders {h} x {w}, view 0 {H} x {W}: all views of a batch must "
+                               "render one size")
+    gt_feats = [None] * V if gt_feats is None else list(gt_feats)
+    with_depth = opt.lambda_depth != 0
+    loss = photometric_loss_views([p["render"] for p in pkgs], [g[:3] for g in gt_images],
+                                  [p["depth"] for p in pkgs] if with_depth else None, list(gt_depths) if with_depth else None,
+                                  [p["feat"] if s else None for p, s in zip(pkgs, sup)],
+                                  [g if s else None for g, s in zip(gt_feats, sup)], lambda_dssim=opt.lambda_dssim,
+                                  lambda_depth=opt.lambda_depth, lambda_feat=opt.lambda_feat if any(sup) else 0.0)
+    fine = "fine" in stage
+    last = pkgs[-1]
+    want_dx = fine and not hyper.no_dx and opt.lambda_dx != 0
+    want_dshs = fine and not hyper.no_dshs and opt.lambda_dshs != 0
+    want_reg = stage == "fine" and hyper.time_smoothness_weight != 0
+    terms, weights = [loss], [1.0]
+    if want_dshs:
+        terms.append(last["dshs_l1"] if "dshs_l1" in last else torch.mean(torch.abs(last["dshs"])))
+        weights.append(float(opt.lambda_dshs))
+    if want_reg:
+        reg = next((p["plane_reg"] for p in pkgs if p.get("plane_reg") is not None), None)
+        terms.append(reg if reg is not None else
+                     pc.compute_regulation(hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight))
+        weights.append(1.0)
+    if len(terms) == 1 and not want_dx:
+        return loss
+    return _WeightedTerms.apply(last["dx"] if want_dx else None, float(opt.lambda_dx), tuple(weights), *terms)
+
+
+def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats, hyper, opt, bg, stage="fine",
+                        pipe: Optional[SimpleNamespace] = None, grad_hook=None, densify_stats=False, optimizer_step=None,
+                        feat_views="last", share_deformation=True):
+    """One iteration of train.py for a batch of V views (opt.batch_size = V, train.py:365-437, 489-493, 521-522): V renders -> one
+    loss (training_loss_views: the reference's batch semantics) -> one backward -> ONE Adam step.  -> (loss, result dicts).
+    Views that share a timestamp (a rig's cameras of one frame) share one deformation pass and one glue pass each way
+    (render_views); views whose feature image gets no loss (all but the last under feat_views="last") do not rasterize one.
+    densify_stats=True: the bookkeeping of train.py:387-388, 435-437, 489-493 in one pass (optim.densify_stats_views): the norm of
+    the SUMMED viewspace gradient, any-visibility, the largest radius.  grad_hook(pc, pkgs) receives the list.
+    share_deformation=False evaluates the field once per view (A/B measurements, equivalence tests).
+    Under run_training_steps an overflow in any view of the batch leaves model and statistics untouched and the whole batch is
+    issued again: the sticky word freezes every later forward of the batch, and the guarded launches read the last one's word."""
+    from . import raster_C
+    from .optim import densify_stats_views as _densify_stats_views
+    pipe = pipe or SimpleNamespace(convert_SHs_python=True, compute_cov3D_python=False, debug=False)
+    cams = list(cams)
+    V = len(cams)
+    if V < 1 or len(gt_images) != V or (gt_depths is not None and len(gt_depths) != V) or (gt_feats is not None and len(gt_feats) != V):
+        raise RuntimeError(f"training_step_views: {V} views need {V} ground-truth images, depths and feature maps (or None)")
+    H, W = int(cams[0]["image_height"]), int(cams[0]["image_width"])
+    for v, cam in enumerate(cams):
+        if (int(cam["image_height"]), int(cam["image_width"])) != (H, W):
+            raise RuntimeError(f"training_step_views: view {v} renders {int(cam['image_height'])} x {int(cam['image_width'])}, "
+                               f"view 0 {H} x {W}: all views of a batch must render one size")
+    sup = _supervised_feat_views(V, hyper, stage, feat_views)
+    pkgs, words = _render_views(cams, pc, pipe, bg, stage, sup, True, share_deformation)
+    loss = training_loss_views(pc, pkgs, gt_images, gt_depths, gt_feats, hyper, opt, stage, feat_views)
+    loss.backward()
+    words = [w for w in words if w is not None]
+    if len(words) > 1 and raster_C.POLICY == "speculative" and not raster_C.REPLAY:
+        # nothing else joins the views' verdicts in this mode: one overflowed view drops the batch's step and statistics
+        raster_C.async_override_skip_flag(pc.get_xyz.device, torch.cat(words).amax(0, keepdim=True))
+    if densify_stats:
+        grads = [p["viewspace_points"].grad if p["viewspace_points"].grad is not None else torch.zeros_like(p["viewspace_points"])
+                 for p in pkgs]
+        if V > 8:      # S3G_DENSIFY_MAX_VIEWS; a larger batch would need its gradients summed first -- not a rig's batch
+            raise RuntimeError("training_step_views(densify_stats=True) serves batches of up to 8 views")
+        _densify_stats_views(pc.xyz_gradient_accum, pc.denom, pc.max_radii2D, grads, [p["radii"] for p in pkgs])
+    if grad_hook is not None:
+        grad_hook(pc, pkgs)
+    if optimizer_step is not None:
+        optimizer_step()
+    else:
+        pc.optimizer.step()
+    pc.optimizer.zero_grad(set_to_none=True)
+    return loss.detach(), pkgs
 
 
 _replay_loop = None      # the _ReplayLoop of the run_training_steps call in progress (surgery_barrier talks to it)

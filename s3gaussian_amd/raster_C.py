@@ -252,6 +252,16 @@ def async_skip_flag(device=None):
     return st.status_dev[st.last_slot:st.last_slot + 1]
 
 
+def async_override_skip_flag(device, word) -> None:
+    """`word` (int32 [1] device tensor) answers async_skip_flag() until the next training forward on `device`: a batch of views that
+    share one optimizer step hands in the maximum of its forwards' words where nothing else joins them (pipeline.training_step_views
+    under the speculative policy outside replay mode; in replay mode the sticky word does, under the verified policy no overflow
+    survives its forward)."""
+    st = _state_of(device)
+    if st is not None:
+        st.flag_override = word
+
+
 def async_status(device=None, block=False) -> dict:
     """Counters of the asynchronous forwards on `device`: calls issued / drained, overflowed calls, mean true instance count of
     the drained calls, capacities per image size.  block=True waits for every outstanding status row first."""
