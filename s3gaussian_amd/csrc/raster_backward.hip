@@ -21,6 +21,8 @@
 #include "geom_math.hpp"
 #include "raster_dev.hpp"
 
+#include "../../include/s3g_alpha.h"
+
 namespace s3g {
 
 // ---- wave64 reduction: inclusive scan with DPP, total lands in lane 63 (LLVM's gfx9 atomic-optimizer sequence) ----
@@ -101,7 +103,11 @@ __device__ __forceinline__ void row_transpose_reduce(const float* v /* [NV] */, 
 // gaussian_renderer/__init__.py:127-166) are back-propagated in ONE pass.  Everything that depends only on the geometry
 // -- the alpha test, exp2, the transmittance recurrence, the six S sums and their wave reductions -- is shared; the second
 // image adds its three colour-gradient sums and its term of dL/dalpha.  Records grow from 10 to 14 floats.
-template <int NX>
+//
+// AL: the accumulated opacity A = 1 - T_final is an output too and dL_dalpha_img [H*W] is its upstream gradient.  The
+// background term below is dL/dT_final * dT_final/dalpha with dL/dT_final = bg . dL_dpixel; a loss on A adds -dL/dA to
+// dL/dT_final, so the gradient enters as bg_dot - dL/dA[pix], once per pixel, and nowhere else.
+template <int NX, bool AL = false>
 __global__ void __launch_bounds__(256)
 blend_backward_kernel(int W, int H, int gx, int tiles, const uint2* __restrict__ ranges,
                       const uint32_t* __restrict__ tile_hi, const uint32_t* __restrict__ point_list,
@@ -110,7 +116,8 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint2* __restrict__
                       const float* __restrict__ depths, const float* __restrict__ final_Ts,
                       const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpixels,
                       const float* __restrict__ dL_dpixel_depths, float* __restrict__ records /*[R][NR]*/,
-                      const float* __restrict__ colors2, const float* __restrict__ dL_dpixels2, int wave_bounds) {
+                      const float* __restrict__ colors2, const float* __restrict__ dL_dpixels2, int wave_bounds,
+                      const float* __restrict__ dL_dalpha_img) {
   constexpr uint32_t BATCH = 32;  // Gaussians staged per round (one bit each in a wave's visit mask)
   constexpr int NR = NX ? NREC + 4 : NREC;
   constexpr int SLOTS = 16;       // 4 waves x 4 rows of 16 lanes
@@ -164,6 +171,7 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint2* __restrict__
   }
   float bg_dot = bg[0] * gr + bg[1] * gg + bg[2] * gb;
   if (NX) bg_dot += bg[0] * g2r + bg[1] * g2g + bg[2] * g2b;
+  if (AL) bg_dot -= inside ? dL_dalpha_img[pix] : 0.f;
 
   float T = T_final;
   float ar = 0.f, ag = 0.f, ab = 0.f, ad = 0.f;  // accum_rec (colour, depth)
@@ -623,13 +631,14 @@ extern "C" size_t s3g_raster_backward2_workspace_bytes(int P, int R) {
   return ((size_t)(R > 0 ? R : 0) * (NREC + 4) * sizeof(float) + 127) & ~size_t(127);
 }
 
-template <int NX>
+template <int NX, bool AL = false>
 static int raster_backward_impl(const char* who, const s3g_raster_inputs* in, const float* colors2, int R, const int* radii,
                                 const void* geometry_arena, const void* binning_arena, const void* image_arena,
                                 void* workspace, const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix2,
                                 float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                                 float* dL_dcolor2, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                                float* dL_dscale, float* dL_drot, const s3g_densify_accum* dens, void* stream_) {
+                                float* dL_dscale, float* dL_drot, const s3g_densify_accum* dens, void* stream_,
+                                const float* dL_dalpha = nullptr) {
   hipStream_t stream = (hipStream_t)stream_;
   if (dens && !(dens->xyz_gradient_accum && dens->denom && dens->max_radii2D)) {
     set_error("%s: s3g_densify_accum needs all three arrays", who);
@@ -643,7 +652,8 @@ static int raster_backward_impl(const char* who, const s3g_raster_inputs* in, co
   if (P == 0) return S3G_OK;
   if (!radii || !geometry_arena || !image_arena || (R > 0 && (!binning_arena || !workspace)) || !dL_dpix ||
       !dL_dpix_depth || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale ||
-      !dL_drot || (in->shs && !dL_dsh) || (NX && (!colors2 || !dL_dpix2 || !dL_dcolor2 || !in->colors_precomp))) {
+      !dL_drot || (in->shs && !dL_dsh) || (NX && (!colors2 || !dL_dpix2 || !dL_dcolor2 || !in->colors_precomp)) ||
+      (AL && !dL_dalpha)) {
     set_error("%s: NULL array argument", who);
     return S3G_ERR_INVALID_ARG;
   }
@@ -659,10 +669,10 @@ static int raster_backward_impl(const char* who, const s3g_raster_inputs* in, co
   if (R > 0) {
     const uint32_t tile_blocks = ((uint32_t)tiles + 7u) & ~7u;
     profile_begin(S3G_PROFILE_BLEND_BACKWARD, stream);
-    hipLaunchKernelGGL(blend_backward_kernel<NX>, dim3(tile_blocks), dim3(256), 0, stream, W, H, gx, tiles, im.ranges,
+    hipLaunchKernelGGL((blend_backward_kernel<NX, AL>), dim3(tile_blocks), dim3(256), 0, stream, W, H, gx, tiles, im.ranges,
                        im.tile_hi, b.point_list, in->background, g.means2D, g.conic_opacity, color_ptr, g.depths,
                        im.final_T, im.n_contrib, dL_dpix, dL_dpix_depth, records, colors2, dL_dpix2,
-                       g_wave_bounds ? 1 : 0);
+                       g_wave_bounds ? 1 : 0, dL_dalpha);
     profile_end(S3G_PROFILE_BLEND_BACKWARD, stream, (double)R, (double)W * H);
     S3G_KERNEL_CHECK(stream, debug);
   }
@@ -729,4 +739,29 @@ extern "C" int s3g_raster_backward2_accum(const s3g_raster_inputs* in, const flo
                                  image_arena, workspace, dL_dpix, dL_dpix_depth, dL_dpix2, dL_dmean2D, dL_dconic, dL_dopacity,
                                  dL_dcolor, dL_dcolor2, dL_ddepth, dL_dmean3D, dL_dcov3D, nullptr, dL_dscale, dL_drot, dens,
                                  stream_);
+}
+
+// The four shapes above with an upstream gradient on the opacity image A = 1 - final_T (include/s3g_alpha.h): one image
+// (colors2 == dL_dpix2 == dL_dcolor2 == NULL; SH colours allowed) or two, with or without the densification bookkeeping.
+extern "C" int s3g_raster_backward_alpha(const s3g_raster_inputs* in, const float* colors2, int R, const int* radii,
+                                         const void* geometry_arena, const void* binning_arena, const void* image_arena,
+                                         void* workspace, const float* dL_dpix, const float* dL_dpix_depth,
+                                         const float* dL_dpix2, const float* dL_dalpha, float* dL_dmean2D, float* dL_dconic,
+                                         float* dL_dopacity, float* dL_dcolor, float* dL_dcolor2, float* dL_ddepth,
+                                         float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                         const s3g_densify_accum* dens, void* stream_) {
+  const char* who = "s3g_raster_backward_alpha";
+  if (dens && !dens->xyz_gradient_accum && !dens->denom && !dens->max_radii2D) dens = nullptr;   // three NULL accumulators = none
+  if ((colors2 != nullptr) != (dL_dpix2 != nullptr) || (colors2 != nullptr) != (dL_dcolor2 != nullptr)) {
+    set_error("%s: colors2, dL_dpix2 and dL_dcolor2 go together (all three or none)", who);
+    return S3G_ERR_INVALID_ARG;
+  }
+  if (colors2)
+    return raster_backward_impl<3, true>(who, in, colors2, R, radii, geometry_arena, binning_arena, image_arena, workspace,
+                                         dL_dpix, dL_dpix_depth, dL_dpix2, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
+                                         dL_dcolor2, dL_ddepth, dL_dmean3D, dL_dcov3D, nullptr, dL_dscale, dL_drot, dens, stream_,
+                                         dL_dalpha);
+  return raster_backward_impl<0, true>(who, in, nullptr, R, radii, geometry_arena, binning_arena, image_arena, workspace,
+                                       dL_dpix, dL_dpix_depth, nullptr, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, nullptr,
+                                       dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dens, stream_, dL_dalpha);
 }

@@ -32,6 +32,7 @@ import torch.nn.functional as F
 from . import lpips as _lpips
 from . import lpips_vgg as _lpips_vgg
 from . import metrics as _metrics
+from . import sky as _sky
 from .deformation import deform_network
 from .glue import activations_and_colors
 from .knn import distCUDA2
@@ -55,7 +56,9 @@ def default_hyper(**over) -> SimpleNamespace:
 
 
 def default_opt(**over) -> SimpleNamespace:
-    """The OptimizationParams the path reads (arguments/__init__.py:100-158)."""
+    """The OptimizationParams the path reads (arguments/__init__.py:100-158).  One extension rides in through `over`:
+    default_opt(lambda_sky=w), the weight of sky.sky_opacity_loss in training_step / training_step_views.  The reference has no such
+    field (its sky masks feed nothing), so the defaults carry none either: an absent lambda_sky is 0, the term is off."""
     o = dict(position_lr_init=0.00016, deformation_lr_init=0.000016, grid_lr_init=0.00016, feature_lr=0.0025,
              opacity_lr=0.05, scaling_lr=0.005, rotation_lr=0.001, lambda_dssim=0.2, lambda_depth=0.5,
              lambda_feat=0.001, lambda_dx=0.001, lambda_dshs=0.001)
@@ -433,7 +436,7 @@ class _LazyResult(dict):
 
 def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torch.Tensor,
            scaling_modifier=1.0, override_color=None, stage="fine", return_decomposition=False, return_dx=False,
-           render_feat=False, densify_accum=None, extra_colors=None):
+           render_feat=False, densify_accum=None, extra_colors=None, return_alpha=False):
     """Mirror of gaussian_renderer/__init__.py::render.  `viewpoint_camera` is a dict with the fields the reference
     reads from a Camera (image_height/width, FoVx/FoVy or tanfovx/tanfovy, world_view_transform=viewmatrix,
     full_proj_transform=projmatrix, camera_center=campos, time).
@@ -443,7 +446,9 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
     extra_colors (extension, no_grad only): a sequence of [P,3] colour tensors.  After the frame's own rasterisation each one is
     blended on the SAME geometry tensors, so the rasterizer's geometry cache serves it without another preprocess / binning / sort
     (s3g_raster_forward_reuse); the images come back as out["extra"], a list of [3,H,W].  What the reference does with one more
-    `render(..., override_color=c)` per image (utils/video_utils.py:267,284), on the fused route and the frame's own geometry."""
+    `render(..., override_color=c)` per image (utils/video_utils.py:267,284), on the fused route and the frame's own geometry.
+    return_alpha (extension): out["alpha"] = the accumulated opacity [1,H,W] of the main render, 1 - the final transmittance of
+    each pixel (rasterizer.forward_alpha); differentiable, zeros for a model without Gaussians.  False launches nothing new."""
     if extra_colors is not None and torch.is_grad_enabled():
         raise RuntimeError("render(extra_colors=...) is an inference extension: call it under torch.no_grad()")
     dev = pc.get_xyz.device
@@ -534,25 +539,32 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
         dynamic_mask = max_values > torch.mean(max_values)
         decomposed = rasterizer.forward_decomposed(means3D=means3D_final, opacities=opacity, dynamic_mask=dynamic_mask,
                                                    shs=shs_final, colors_precomp=colors_precomp, scales=scales_final,
-                                                   rotations=rotations_final, cov3D_precomp=cov3D_precomp)
+                                                   rotations=rotations_final, cov3D_precomp=cov3D_precomp,
+                                                   **({"with_alpha": True} if return_alpha else {}))
     pair = want_feat and colors_precomp is not None and means3D_final.is_cuda and getattr(pipe, "fused_pair", True)
     # the bookkeeping rides in the pair node's backward only when that node really is the fused one (forward_pair falls back to
     # two ordinary nodes for P == 0 or debug snapshots); otherwise training_step runs the separate pass (optim.densify_stats)
     fuse_stats = bool(densify_accum is not None and pair and means3D_final.shape[0] > 0 and not rs.debug)
+    alpha = None
     if decomposed is not None:
         rendered_image, radii, depth = decomposed["render"], decomposed["radii"], decomposed["depth"]
+        alpha = decomposed.get("alpha")
     elif pair:
         # RGB + feature image from one node: shared geometry forward, ONE fused backward (rasterizer.forward_pair)
-        rendered_image, radii, depth, rendered_image2 = rasterizer.forward_pair(
+        rendered_image, radii, depth, rendered_image2, *alpha = rasterizer.forward_pair(
             means3D=means3D_final, means2D=means2D, opacities=opacity, colors_a=colors_precomp, colors_b=feat,
             scales=scales_final, rotations=rotations_final, cov3D_precomp=cov3D_precomp,
-            densify_accum=densify_accum if fuse_stats else None)
+            densify_accum=densify_accum if fuse_stats else None, **({"with_alpha": True} if return_alpha else {}))
+        alpha = alpha[0] if alpha else None
     else:
-        rendered_image, radii, depth = rasterizer(means3D=means3D_final, means2D=means2D, shs=shs_final,
-                                                  colors_precomp=colors_precomp, opacities=opacity, scales=scales_final,
-                                                  rotations=rotations_final, cov3D_precomp=cov3D_precomp)
+        rendered_image, radii, depth, *alpha = (rasterizer.forward_alpha if return_alpha else rasterizer)(
+            means3D=means3D_final, means2D=means2D, shs=shs_final, colors_precomp=colors_precomp, opacities=opacity,
+            scales=scales_final, rotations=rotations_final, cov3D_precomp=cov3D_precomp)
+        alpha = alpha[0] if alpha else None
     out = _LazyResult({"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
                        "radii": radii, "depth": depth})
+    if return_alpha:
+        out["alpha"] = alpha
     if densify_accum is not None:
         out["densify_stats_fused"] = fuse_stats
     if want_feat:
@@ -719,7 +731,7 @@ def _fused_route_missing(pc: GaussianParams, pipe: SimpleNamespace) -> str:
 
 @torch.no_grad()
 def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.Tensor, num_cams: int = 3, sink=None,
-                 with_rgb: bool = False, return_decomposition: bool = False, on_frame=None) -> Dict:
+                 with_rgb: bool = False, return_decomposition: bool = False, on_frame=None, return_alpha: bool = False) -> Dict:
     """The forward and backward scene-flow images of the reference's evaluation loop (utils/video_utils.py:203-209, 252-299): frame t,
     rendered in stage "fine" at its own camera and time, painted with C(dx[t + n] - dx[t]) and C(dx[t] - dx[t - n]) (flow.frame_plan,
     n = num_cams; C = flow.scene_flow_colors).  `cameras` in dataset order: num_cams cameras per timestamp.
@@ -737,7 +749,7 @@ def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.T
     reference's lists hold `image.permute(1, 2, 0).cpu().numpy()` of the same images ([H,W,3]).
     sink(kind, frame_index, image), kind in ("forward", "backward", "rgb"): every image is handed over as soon as it exists and none
     is kept (the lists come back empty): 150 frames x 2 x 20 MB need not stay resident.
-    return_decomposition is passed on to each frame's render(); on_frame(i, pkg) is called with frame i's full render result (its
+    return_decomposition and return_alpha are passed on to each frame's render(); on_frame(i, pkg) is called with frame i's full render result (its
     "extra" holds the forward flow image first and the backward one last) before the images are delivered: evaluate_video hangs the
     rest of the evaluation on the same render this way.
     Needs the fused deformation route (the reference's default head configuration, SH degree 3, on the GPU): there is no second
@@ -779,7 +791,8 @@ def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.T
             if pair not in colors:
                 colors[pair] = _flow.scene_flow_colors(window[pair[0]], window[pair[1]])
         unique = [colors[pairs[0]]] + ([colors[pairs[1]]] if pairs[1] != pairs[0] else [])
-        pkg = render(cam, pc, pipe, bg, stage="fine", return_decomposition=return_decomposition, extra_colors=unique)
+        pkg = render(cam, pc, pipe, bg, stage="fine", return_decomposition=return_decomposition, extra_colors=unique,
+                     **({"return_alpha": True} if return_alpha else {}))
         if on_frame is not None:
             on_frame(i, pkg)
         if with_rgb:
@@ -822,12 +835,14 @@ def save_split_point_clouds(pc: GaussianParams, time: float, dynamic_pcd_path: s
 
 
 VIDEO_KEYS = ("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs", "forward_flows", "backward_flows")
-_VIDEO_SOURCE = {"rgbs": "render", "depths": "depth", "dynamic_rgbs": "render_d", "static_rgbs": "render_s"}
+SKY_VIDEO_KEYS = ("opacities", "sky_masks", "gt_sky_masks")       # asked for through evaluate_video(sky_keys=...), not through keys=
+_VIDEO_SOURCE = {"rgbs": "render", "depths": "depth", "dynamic_rgbs": "render_d", "static_rgbs": "render_s", "opacities": "alpha"}
+_VIDEO_ONE_CHANNEL = ("depths", "opacities")
 
 
 def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: torch.Tensor, masks=None, num_cams: int = 3,
                    keys=("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs"), sink=None, host: bool = False,
-                   compute_metrics: bool = True, stage: str = "fine", lpips=None) -> Dict:
+                   compute_metrics: bool = True, stage: str = "fine", lpips=None, sky_keys=(), sky_masks=None) -> Dict:
     """The reference's evaluation loop with its videos' frames (utils/video_utils.py:116-349 render_func, then 439-499
     save_seperate_videos) from ONE render per camera: render(cam, return_decomposition=<a decomposition key is asked for>,
     extra_colors=<the frame's flow colours, if a flow key is asked for>) feeds metrics.image_metrics -- row i of the [N,5] table,
@@ -835,7 +850,14 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     timestamp (i // num_cams)'s strips; the fp32 images are dropped right after.
 
     keys: any of VIDEO_KEYS.  A strip is the [H, num_cams * W, C] uint8 array the reference appends to the key's video writer for
-    one timestamp -- to8b of the cameras' images side by side; C = 1 for "depths", whose frames are each divided by their own maximum.
+    one timestamp -- to8b of the cameras' images side by side; C = 1 for "depths", whose frames are each divided by their own maximum,
+    and for "opacities".
+    sky_keys: any of SKY_VIDEO_KEYS, delivered like the keys of `keys` and behind them (frames, middle, sink; `keys` itself goes on
+    accepting the seven names the reference's render_func fills and refusing every other; both together at most 8 strips).
+    "opacities", "sky_masks", "gt_sky_masks" are the keys save_seperate_videos has code for (utils/video_utils.py:461-471) and the
+    reference's render_func never fills: the accumulated opacity of each render (render(return_alpha=True)); 1 - opacity, evaluated in
+    fp32 from the opacity image and replicated to three channels (`1 - np.stack([frame] * 3, axis=-1)`); and the caller's
+    `sky_masks` (one [H,W] / [1,H,W] tensor per camera, required by "gt_sky_masks"), replicated likewise.
     T = len(cameras) // num_cams timestamps; leftover cameras are rendered and counted in the metrics and appear in no strip.
     When a timestamp's last camera has been composed each of its strips goes to sink(key, timestamp_index, strip), in the order of
     `keys`; without a sink into result["frames"][key] (with one, those lists stay empty).  result["middle"][key] is the strip of
@@ -851,10 +873,15 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     Flow keys run the loop through render_flows (its windowing of dx and colours; stage "fine", at least 2 * num_cams cameras); they
     and the decomposition keys need the fused deformation route, as render_flows does."""
     from . import frames as _frames
-    keys = tuple(keys)
+    keys, sky_keys = tuple(keys), tuple(sky_keys)
     unknown = [k for k in keys if k not in VIDEO_KEYS]
-    if unknown or not keys or len(set(keys)) != len(keys) or len(keys) > _frames.MAX_JOBS:
-        raise RuntimeError(f"evaluate_video: keys must be distinct entries of {VIDEO_KEYS} (got {keys})")
+    if unknown or not (keys or sky_keys) or len(set(keys)) != len(keys) or len(keys) > _frames.MAX_JOBS:
+        raise RuntimeError(f"evaluate_video: keys must be distinct entries of {VIDEO_KEYS} (got {keys}); "
+                           f"{SKY_VIDEO_KEYS} are asked for through sky_keys=")
+    if any(k not in SKY_VIDEO_KEYS for k in sky_keys) or len(set(sky_keys)) != len(sky_keys) or len(keys) + len(sky_keys) > _frames.MAX_JOBS:
+        raise RuntimeError(f"evaluate_video: sky_keys must be distinct entries of {SKY_VIDEO_KEYS} (got {sky_keys}), and keys and "
+                           f"sky_keys together at most {_frames.MAX_JOBS}")
+    keys = keys + sky_keys
     n, N = int(num_cams), len(cameras)
     if n == 5:
         raise RuntimeError("evaluate_video: num_cams = 5 is refused: the reference rescales the two outer views of five with "
@@ -863,6 +890,9 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
         raise RuntimeError(f"evaluate_video: num_cams = {num_cams}")
     if len(gt_images) != N or (masks is not None and len(masks) != N):
         raise RuntimeError("evaluate_video: one ground-truth image (and one mask entry) per camera")
+    if "gt_sky_masks" in keys and (sky_masks is None or len(sky_masks) != N):
+        raise RuntimeError('evaluate_video: the sky key "gt_sky_masks" needs sky_masks=, one mask per camera')
+    want_alpha = any(k in ("opacities", "sky_masks") for k in keys)
     want_flow = any(k in ("forward_flows", "backward_flows") for k in keys)
     want_dec = any(k in ("dynamic_rgbs", "static_rgbs") for k in keys)
     if (want_flow or want_dec) and not (_fused_route(pc, pipe) and "fine" in stage):
@@ -926,7 +956,7 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
             return
         if c == 0:
             state.size = (H, W)
-            state.strips = [torch.empty(_frames.strip_shape(H, W, 1 if k == "depths" else 3, n), dtype=torch.uint8, device=dev)
+            state.strips = [torch.empty(_frames.strip_shape(H, W, 1 if k in _VIDEO_ONE_CHANNEL else 3, n), dtype=torch.uint8, device=dev)
                             for k in keys]
         elif state.size != (H, W):
             raise RuntimeError(f"evaluate_video: camera {i} renders {H} x {W}, the first camera of its timestamp "
@@ -939,6 +969,13 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
                 images.append(pkg["extra"][0])
             elif k == "backward_flows":
                 images.append(pkg["extra"][-1])
+            elif k == "sky_masks":           # prepared outside frames.compose: 1 - opacity in fp32, three equal channels
+                images.append((1.0 - pkg["alpha"]).expand(3, H, W))
+            elif k == "gt_sky_masks":
+                m = sky_masks[i]
+                if not torch.is_tensor(m) or m.numel() != H * W:
+                    raise RuntimeError(f"evaluate_video: sky_masks[{i}] must be a tensor of {H} x {W} elements")
+                images.append(m.to(dev).float().reshape(1, H, W).expand(3, H, W))
             else:
                 if _VIDEO_SOURCE[k] not in pkg:
                     raise RuntimeError(f'evaluate_video: render() returned no "{_VIDEO_SOURCE[k]}" for key "{k}" on this route')
@@ -951,10 +988,11 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     with torch.no_grad():
         if want_flow:
             render_flows(pc, cameras, pipe, bg, num_cams=n, sink=lambda kind, i, image: None, return_decomposition=want_dec,
-                         on_frame=on_frame)
+                         on_frame=on_frame, **({"return_alpha": True} if want_alpha else {}))
         else:
             for i, cam in enumerate(cameras):
-                on_frame(i, render(cam, pc, pipe, bg, stage=stage, return_decomposition=want_dec))
+                on_frame(i, render(cam, pc, pipe, bg, stage=stage, return_decomposition=want_dec,
+                                   **({"return_alpha": True} if want_alpha else {})))
         drain(state.pending)
     if not compute_metrics:
         result.update({"psnr": -1, "ssim": -1, "masked_psnr": -1, "masked_ssim": -1, "per_frame": None})
@@ -1007,9 +1045,20 @@ class _WeightedTerms(torch.autograd.Function):
         return (g_dx, None, None, *(gi.reshape(sh) for gi, sh in zip(gw[:ctx.n].unbind(0), ctx.term_shapes)))
 
 
-def training_loss(pc: GaussianParams, pkg: Dict, gt_image, gt_depth, gt_feat, hyper, opt, stage="fine", fused_pixel_terms=True):
+def _sky_weight(opt, sky_mask) -> float:
+    """lambda_sky if the sky term is on (a mask was handed in and the weight is not 0), else 0."""
+    return float(getattr(opt, "lambda_sky", 0.0)) if sky_mask is not None else 0.0
+
+
+def training_loss(pc: GaussianParams, pkg: Dict, gt_image, gt_depth, gt_feat, hyper, opt, stage="fine", fused_pixel_terms=True,
+                  sky_mask=None):
     """train.py:395-425 for a batch of one view.  The per-pixel terms (L1, depth L2, DSSIM, feature L2) run as one fused
-    pass (losses.photometric_loss); fused_pixel_terms=False evaluates them step by step like the reference."""
+    pass (losses.photometric_loss); fused_pixel_terms=False evaluates them step by step like the reference.
+    sky_mask ([H,W] / [1,H,W], 1 = sky) with opt.lambda_sky != 0 adds lambda_sky * sky.sky_opacity_loss(pkg["alpha"], sky_mask)
+    (an extension: the package must come from render(return_alpha=True))."""
+    lam_sky = _sky_weight(opt, sky_mask)
+    if lam_sky != 0.0 and pkg.get("alpha") is None:
+        raise RuntimeError('training_loss: the sky term needs pkg["alpha"]: render(..., return_alpha=True)')
     fine = "fine" in stage
     use_feat = stage == "fine" and hyper.feat_head
     if fused_pixel_terms:
@@ -1038,8 +1087,13 @@ def training_loss(pc: GaussianParams, pkg: Dict, gt_image, gt_depth, gt_feat, hy
         if want_reg:
             loss = loss + (pkg["plane_reg"] if pkg.get("plane_reg") is not None else
                            pc.compute_regulation(hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight))
+        if lam_sky != 0.0:
+            loss = loss + _sky.sky_opacity_loss(pkg["alpha"], sky_mask, lam_sky)
         return loss
     terms, weights = [loss], [1.0]
+    if lam_sky != 0.0:
+        terms.append(_sky.sky_opacity_loss(pkg["alpha"], sky_mask, 1.0))
+        weights.append(lam_sky)
     if want_dshs:
         terms.append(pkg["dshs_l1"] if "dshs_l1" in pkg else torch.mean(torch.abs(pkg["dshs"])))
         weights.append(float(opt.lambda_dshs))
@@ -1053,7 +1107,7 @@ def training_loss(pc: GaussianParams, pkg: Dict, gt_image, gt_depth, gt_feat, hy
 
 
 def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hyper, opt, bg, stage="fine",
-                  pipe: Optional[SimpleNamespace] = None, grad_hook=None, densify_stats=False, optimizer_step=None):
+                  pipe: Optional[SimpleNamespace] = None, grad_hook=None, densify_stats=False, optimizer_step=None, sky_mask=None):
     """One iteration of train.py for one view: render -> loss -> backward -> Adam step.  `grad_hook(pc, pkg)` runs
     between backward and the optimizer step (used by the data-parallel wrapper for the RCCL all-reduce).
     densify_stats=True also does the bookkeeping of train.py:489-493 (max_radii2D, xyz_gradient_accum, denom) for this
@@ -1061,12 +1115,16 @@ def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hy
     (the default fine-stage configuration), else -- coarse stage, pipe.fused_pair=False, debug snapshots, P == 0 -- as one fused
     pass over the viewspace gradient afterwards (optim.densify_stats).  Data-parallel runs reduce the statistics first
     (dp.reduce_densification_stats) and must leave this off.  `optimizer_step()` replaces `pc.optimizer.step()` (data parallel:
-    dp.OverlappedGradAllReducer.finish_and_step, which steps the early-reduced groups while the last collectives are in flight)."""
+    dp.OverlappedGradAllReducer.finish_and_step, which steps the early-reduced groups while the last collectives are in flight).
+    sky_mask with opt.lambda_sky != 0 (extension): the render also returns its opacity image and the loss gains
+    lambda_sky * sky.sky_opacity_loss; its gradient rides in the same rasterizer backward, fused densify statistics included.
+    Without a mask, or with lambda_sky = 0, nothing new is launched."""
     pipe = pipe or SimpleNamespace(convert_SHs_python=True, compute_cov3D_python=False, debug=False)
     acc = (pc.xyz_gradient_accum, pc.denom, pc.max_radii2D) if densify_stats else None
+    want_sky = _sky_weight(opt, sky_mask) != 0.0
     pkg = render(cam, pc, pipe, bg, stage=stage, return_dx=True, render_feat=(stage == "fine" and hyper.feat_head),
-                 densify_accum=acc)
-    loss = training_loss(pc, pkg, gt_image, gt_depth, gt_feat, hyper, opt, stage)
+                 densify_accum=acc, **({"return_alpha": True} if want_sky else {}))
+    loss = training_loss(pc, pkg, gt_image, gt_depth, gt_feat, hyper, opt, stage, **({"sky_mask": sky_mask} if want_sky else {}))
     loss.backward()
     if densify_stats and not pkg.get("densify_stats_fused", False):
         from .optim import densify_stats as _densify_stats
@@ -1110,7 +1168,7 @@ def _views_on_fused_route(pc: GaussianParams, pipe: SimpleNamespace, stage: str)
                 and ("coarse" in stage or net._fused_any()))
 
 
-def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation):
+def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation, return_alpha=False):
     """-> (result dicts, the skip word of each view's asynchronous forward or None)."""
     from . import raster_C
     from .glue import MAX_VIEWS, activations_and_colors_views
@@ -1124,7 +1182,8 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
     if not _views_on_fused_route(pc, pipe, stage):
         outs, words = [], []
         for cam, f in zip(cams, flags):     # the library route: nothing to share, the same results contract
-            outs.append(render(cam, pc, pipe, bg_color, stage=stage, return_dx=return_dx, render_feat=f))
+            outs.append(render(cam, pc, pipe, bg_color, stage=stage, return_dx=return_dx, render_feat=f,
+                               **({"return_alpha": True} if return_alpha else {})))
             words.append(raster_C.async_skip_flag(dev) if dev.type == "cuda" else None)
         return outs, words
     groups: Dict[float, list] = {}
@@ -1171,13 +1230,14 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
             want_feat = flags[i] and "fine" in stage
             # densify_accum is never handed over: a batch's statistics take the norm of the SUMMED viewspace gradient
             if want_feat and getattr(pipe, "fused_pair", True):
-                image, radii, depth, image2 = rasterizer.forward_pair(
+                image, radii, depth, image2, *alpha = rasterizer.forward_pair(
                     means3D=means3D_final, means2D=means2D, opacities=opacity_final, colors_a=colors[k], colors_b=feat,
-                    scales=scales_final, rotations=rotations_final, cov3D_precomp=None, densify_accum=None)
+                    scales=scales_final, rotations=rotations_final, cov3D_precomp=None, densify_accum=None,
+                    **({"with_alpha": True} if return_alpha else {}))
             else:
-                image, radii, depth = rasterizer(means3D=means3D_final, means2D=means2D, shs=None, colors_precomp=colors[k],
-                                                 opacities=opacity_final, scales=scales_final, rotations=rotations_final,
-                                                 cov3D_precomp=None)
+                image, radii, depth, *alpha = (rasterizer.forward_alpha if return_alpha else rasterizer)(
+                    means3D=means3D_final, means2D=means2D, shs=None, colors_precomp=colors[k], opacities=opacity_final,
+                    scales=scales_final, rotations=rotations_final, cov3D_precomp=None)
                 if want_feat:
                     image2, _, _ = rasterizer(means3D=means3D_final, means2D=means2D, shs=None, colors_precomp=feat,
                                               opacities=opacity_final, scales=scales_final, rotations=rotations_final,
@@ -1187,6 +1247,8 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
                                "depth": depth})
             if want_feat:
                 out["feat"] = image2
+            if return_alpha:
+                out["alpha"] = alpha[0]
             if return_dx and "fine" in stage:
                 out.update({"dx": dx, "dshs": dshs})
                 if dshs_l1 is not None:
@@ -1198,7 +1260,7 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
 
 
 def render_views(cams, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torch.Tensor, stage="fine", render_feat=False,
-                 return_dx=True, share_deformation=True):
+                 return_dx=True, share_deformation=True, return_alpha=False):
     """render() for a batch of views -> a list of result dicts with the keys render() returns, in the order of `cams`.
     The deformation field depends on (xyz, t) only, never on the camera.  On the fused route (stage "coarse", or a network on
     Deformation._fused_any with the fused glue: every head subset, no_dx, the geometry heads) the views are grouped by cam["time"]
@@ -1212,8 +1274,9 @@ def render_views(cams, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torc
     tests).  On the library route (grid_pe, no_grid, static_mlp, empty_voxel, pipe.fused_glue=False, convert_SHs_python=False,
     compute_cov3D_python) this is one render() per view: same contract, nothing shared.
     No densify_accum here: a batch's densification statistics take the norm of the summed viewspace gradient
-    (optim.densify_stats_views), which a per-view update inside the rasterizer's backward cannot give."""
-    return _render_views(list(cams), pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation)[0]
+    (optim.densify_stats_views), which a per-view update inside the rasterizer's backward cannot give.
+    return_alpha: every dict carries "alpha", as render(return_alpha=True) gives it."""
+    return _render_views(list(cams), pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation, bool(return_alpha))[0]
 
 
 def _supervised_feat_views(V: int, hyper, stage: str, feat_views: str):
@@ -1223,7 +1286,8 @@ def _supervised_feat_views(V: int, hyper, stage: str, feat_views: str):
     return [bool(use_feat and (feat_views == "all" or v == V - 1)) for v in range(V)]
 
 
-def training_loss_views(pc: GaussianParams, pkgs, gt_images, gt_depths, gt_feats, hyper, opt, stage="fine", feat_views="last"):
+def training_loss_views(pc: GaussianParams, pkgs, gt_images, gt_depths, gt_feats, hyper, opt, stage="fine", feat_views="last",
+                        sky_masks=None):
     """train.py:389-425 for a batch of V views, the reference's semantics line for line, quirks included:
       - L1 and SSIM are means over all V*3*H*W elements of the concatenated images;
       - the depth term is the mean over the valid pixels of the WHOLE batch (one joint count, not a mean of per-view means);
@@ -1231,9 +1295,15 @@ def training_loss_views(pc: GaussianParams, pkgs, gt_images, gt_depths, gt_feats
         (the reference reads `render_pkg` after its loop);
       - the plane regulariser is applied once.
     feat_views="all" (an extension for rigs whose every camera has a feature map, NOT the reference's behaviour) supervises every
-    view's feature image instead: the mean over V*3*H*W.  One fused node for the per-pixel terms (losses.photometric_loss_views)."""
+    view's feature image instead: the mean over V*3*H*W.  One fused node for the per-pixel terms (losses.photometric_loss_views).
+    sky_masks (one per view) with opt.lambda_sky != 0 (extension) adds lambda_sky * the sky cross entropy as ONE mean over
+    V*H*W: every view is supervised, each with weight 1/V (sky.sky_opacity_loss)."""
     from .losses import photometric_loss_views
     V = len(pkgs)
+    lam_sky = _sky_weight(opt, sky_masks)
+    if lam_sky != 0.0 and (len(sky_masks) != V or any(p.get("alpha") is None for p in pkgs)):
+        raise RuntimeError(f'training_loss_views: the sky term needs {V} sky masks and "alpha" in every package '
+                           "(render_views(..., return_alpha=True))")
     if V < 1 or len(gt_images) != V:
         raise RuntimeError(f"training_loss_views: {V} views, {len(gt_images)} ground-truth images")
     sup = _supervised_feat_views(V, hyper, stage, feat_views)
@@ -1256,6 +1326,9 @@ def training_loss_views(pc: GaussianParams, pkgs, gt_images, gt_depths, gt_feats
     want_dshs = fine and not hyper.no_dshs and opt.lambda_dshs != 0
     want_reg = stage == "fine" and hyper.time_smoothness_weight != 0
     terms, weights = [loss], [1.0]
+    if lam_sky != 0.0:
+        terms.append(_sky.sky_opacity_loss([p["alpha"] for p in pkgs], list(sky_masks), 1.0))
+        weights.append(lam_sky)
     if want_dshs:
         terms.append(last["dshs_l1"] if "dshs_l1" in last else torch.mean(torch.abs(last["dshs"])))
         weights.append(float(opt.lambda_dshs))
@@ -1271,7 +1344,7 @@ def training_loss_views(pc: GaussianParams, pkgs, gt_images, gt_depths, gt_feats
 
 def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats, hyper, opt, bg, stage="fine",
                         pipe: Optional[SimpleNamespace] = None, grad_hook=None, densify_stats=False, optimizer_step=None,
-                        feat_views="last", share_deformation=True):
+                        feat_views="last", share_deformation=True, sky_masks=None):
     """One iteration of train.py for a batch of V views (opt.batch_size = V, train.py:365-437, 489-493, 521-522): V renders -> one
     loss (training_loss_views: the reference's batch semantics) -> one backward -> ONE Adam step.  -> (loss, result dicts).
     Views that share a timestamp (a rig's cameras of one frame) share one deformation pass and one glue pass each way
@@ -1280,7 +1353,8 @@ def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats
     the SUMMED viewspace gradient, any-visibility, the largest radius.  grad_hook(pc, pkgs) receives the list.
     share_deformation=False evaluates the field once per view (A/B measurements, equivalence tests).
     Under run_training_steps an overflow in any view of the batch leaves model and statistics untouched and the whole batch is
-    issued again: the sticky word freezes every later forward of the batch, and the guarded launches read the last one's word."""
+    issued again: the sticky word freezes every later forward of the batch, and the guarded launches read the last one's word.
+    sky_masks (one per view) with opt.lambda_sky != 0: see training_loss_views; otherwise nothing new is launched."""
     from . import raster_C
     from .optim import densify_stats_views as _densify_stats_views
     pipe = pipe or SimpleNamespace(convert_SHs_python=True, compute_cov3D_python=False, debug=False)
@@ -1294,8 +1368,10 @@ def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats
             raise RuntimeError(f"training_step_views: view {v} renders {int(cam['image_height'])} x {int(cam['image_width'])}, "
                                f"view 0 {H} x {W}: all views of a batch must render one size")
     sup = _supervised_feat_views(V, hyper, stage, feat_views)
-    pkgs, words = _render_views(cams, pc, pipe, bg, stage, sup, True, share_deformation)
-    loss = training_loss_views(pc, pkgs, gt_images, gt_depths, gt_feats, hyper, opt, stage, feat_views)
+    want_sky = _sky_weight(opt, sky_masks) != 0.0
+    pkgs, words = _render_views(cams, pc, pipe, bg, stage, sup, True, share_deformation, want_sky)
+    loss = training_loss_views(pc, pkgs, gt_images, gt_depths, gt_feats, hyper, opt, stage, feat_views,
+                               **({"sky_masks": sky_masks} if want_sky else {}))
     loss.backward()
     words = [w for w in words if w is not None]
     if len(words) > 1 and raster_C.POLICY == "speculative" and not raster_C.REPLAY:

@@ -681,6 +681,71 @@ def rasterize_gaussians_backward2(background, means3D, radii, colors, colors2, s
             v["means3D"].view(P, 3), v["cov3D"].view(P, 6), v["scales"].view(P, 3), v["rot"].view(P, 4))
 
 
+def raster_alpha(imageBuffer, image_height, image_width):
+    """Extension: the accumulated opacity A = 1 - final_T [1,H,W] of the forward that filled `imageBuffer`
+    (include/s3g_alpha.h::s3g_raster_alpha).  An empty buffer (the P == 0 early-out blended nothing) gives zeros."""
+    H, W = int(image_height), int(image_width)
+    if imageBuffer.numel() == 0:
+        return torch.zeros((1, H, W), dtype=torch.float32, device=imageBuffer.device)
+    _require_gpu(imageBuffer, "imageBuffer")
+    if imageBuffer.numel() * imageBuffer.element_size() < 4 * H * W:
+        raise RuntimeError(f"raster_alpha: the image arena is smaller than a {H} x {W} transmittance image")
+    out = torch.empty((1, H, W), dtype=torch.float32, device=imageBuffer.device)
+    with _lib.on_device(imageBuffer.device):
+        code = _lib.lib().s3g_raster_alpha(W, H, imageBuffer.data_ptr(), out.data_ptr(), _lib.stream_ptr())
+    _lib.check(code)
+    return out
+
+
+def rasterize_gaussians_backward_alpha(background, means3D, radii, colors, colors2, scales, rotations, scale_modifier,
+                                       cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
+                                       dL_dout_color2, dL_dout_alpha, sh, degree, campos, geomBuffer, R, binningBuffer,
+                                       imageBuffer, debug, densify_accum=None, return_internals=False):
+    """Backward of one render (colors2 = dL_dout_color2 = None) or of two renders of the same geometry, with an upstream gradient
+    dL_dout_alpha [1,H,W] on the opacity image as well (include/s3g_alpha.h::s3g_raster_backward_alpha).
+    -> (dL_dmeans2D, dL_dcolors, dL_dcolors2 | None, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations);
+    return_internals=True appends (dL_dconic[P,2,2], dL_ddepths[P,1]) like rasterize_gaussians_backward."""
+    L = _lib.lib()
+    dev = means3D.device
+    P = means3D.size(0)
+    H, W = dL_dout_color.size(1), dL_dout_color.size(2)
+    two = colors2 is not None
+    M = sh.size(1) if (not two and sh.numel() != 0) else 0
+    v = _grad_slab(P, M, dev, return_internals)
+    g_col2 = torch.empty((P, NUM_CHANNELS), dtype=torch.float32, device=dev) if two else None
+    if P != 0:
+        if tuple(dL_dout_alpha.shape[-2:]) != (H, W) or dL_dout_alpha.numel() != H * W:
+            raise RuntimeError(f"dL_dout_alpha must have {H} x {W} elements")
+        empty = torch.Tensor([])
+        keep = [_f32(background, "bg"), _f32(means3D, "means3D"), _f32(sh if not two else empty, "sh"),
+                _f32(colors, "colors_precomp"), _f32(colors2 if two else empty, "colors2"), _f32(scales, "scales"),
+                _f32(rotations, "rotations"), _f32(cov3D_precomp, "cov3D_precomp"), _f32(viewmatrix, "viewmatrix"),
+                _f32(projmatrix, "projmatrix"), _f32(campos, "campos"), _f32(dL_dout_color, "dL_dout_color"),
+                _f32(dL_dout_depth, "dL_dout_depth"), _f32(dL_dout_color2 if two else empty, "dL_dout_color2"),
+                _f32(dL_dout_alpha, "dL_dout_alpha"), radii.contiguous()]
+        bg_, m3_, sh_, col_, col2_, sc_, rot_, cov_, view_, proj_, cam_, gcol_, gdep_, gcol2_, galpha_, radii_ = keep
+        inp = _inputs(P, degree if not two else 0, M, W, H, bg_, m3_, sh_, col_, None, sc_, scale_modifier, rot_, cov_, view_,
+                      proj_, tan_fovx, tan_fovy, cam_, False, debug)
+        nbytes = (L.s3g_raster_backward2_workspace_bytes if two else L.s3g_raster_backward_workspace_bytes)(P, int(R))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dens = C.byref(_densify_struct(densify_accum, P)) if densify_accum is not None else None
+        with _lib.on_device(dev):
+            code = L.s3g_raster_backward_alpha(
+                C.byref(inp), _ptr(col2_) or None, int(R), radii_.data_ptr(), _ptr(geomBuffer), _ptr(binningBuffer),
+                _ptr(imageBuffer), _ptr(work), gcol_.data_ptr(), gdep_.data_ptr(), _ptr(gcol2_) or None, galpha_.data_ptr(),
+                v["means2D"].data_ptr(), _ptr(v["conic"]) or None, v["opacity"].data_ptr(), v["colors"].data_ptr(),
+                g_col2.data_ptr() if two else None, _ptr(v["depths"]) or None, v["means3D"].data_ptr(), v["cov3D"].data_ptr(), _ptr(v["sh"]) or None,
+                v["scales"].data_ptr(), v["rot"].data_ptr(), dens, _lib.stream_ptr())
+        _lib.check(code)
+    elif two:
+        g_col2.zero_()
+    out = (v["means2D"].view(P, 3), v["colors"].view(P, NUM_CHANNELS), g_col2, v["opacity"].view(P, 1), v["means3D"].view(P, 3),
+           v["cov3D"].view(P, 6), v["sh"].view(P, M, 3), v["scales"].view(P, 3), v["rot"].view(P, 4))
+    if return_internals:
+        out = out + (v["conic"].view(P, 2, 2), v["depths"].view(P, 1))
+    return out
+
+
 def _densify_struct(acc, P) -> _lib.DensifyAccum:
     a, d, m = acc
     for name, t_ in (("xyz_gradient_accum", a), ("denom", d), ("max_radii2D", m)):

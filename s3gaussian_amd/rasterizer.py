@@ -39,6 +39,13 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                 forward_only=False):
+        return _RasterizeGaussians._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                            cov3Ds_precomp, raster_settings, forward_only)[:3]
+
+    @staticmethod
+    def _forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                 forward_only):
+        """-> (color, radii, depth, image arena): the body both single-image nodes share."""
         rs = raster_settings
         native_args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                        rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
@@ -59,7 +66,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.num_rendered = num_rendered
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
         ctx.mark_non_differentiable(radii)
-        return color, radii, depth
+        return color, radii, depth, img
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_out_depth):
@@ -95,6 +102,13 @@ class _RasterizeGaussiansPair(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                 densify_accum=None, forward_only=False):
+        return _RasterizeGaussiansPair._forward(ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations,
+                                                cov3Ds_precomp, raster_settings, densify_accum, forward_only)[:4]
+
+    @staticmethod
+    def _forward(ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                 densify_accum, forward_only):
+        """-> (color, radii, depth, color2, image arena): the body both two-image nodes share."""
         rs = raster_settings
         empty = torch.Tensor([])
         common = (opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
@@ -106,7 +120,7 @@ class _RasterizeGaussiansPair(torch.autograd.Function):
         ctx.densify_accum = densify_accum
         ctx.save_for_backward(colors_a, colors_b, means3D, scales, rotations, cov3Ds_precomp, radii, geom, binning, img)
         ctx.mark_non_differentiable(radii)
-        return color, radii, depth, color2
+        return color, radii, depth, color2, img
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth, grad_color2):
@@ -120,6 +134,66 @@ class _RasterizeGaussiansPair(torch.autograd.Function):
             rs.bg, means3D, radii, colors_a, colors_b, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_color2, rs.campos, geom, ctx.num_rendered,
             binning, img, rs.debug, densify_accum=ctx.densify_accum)
+        return g_means3D, g_means2D, g_col_a, g_col_b, g_opac, g_scales, g_rot, g_cov3D, None, None, None
+
+
+class _RasterizeGaussiansAlpha(torch.autograd.Function):
+    """_RasterizeGaussians with the accumulated opacity A = 1 - final_T as a fourth, differentiable output: one image-sized
+    pass forward (s3g_raster_alpha), and a backward that hands grad_alpha to the blend backward (s3g_raster_backward_alpha).
+    Without a gradient on A the backward is _RasterizeGaussians' own."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                forward_only=False):
+        ctx.set_materialize_grads(False)      # an output that feeds no loss arrives as None in backward, not as a zero image
+        color, radii, depth, img = _RasterizeGaussians._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales,
+                                                                rotations, cov3Ds_precomp, raster_settings, forward_only)
+        rs = raster_settings
+        return color, radii, depth, _C.raster_alpha(img, rs.image_height, rs.image_width)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, grad_alpha):
+        if grad_alpha is None:
+            return _RasterizeGaussians.backward(ctx, grad_out_color, _grad_radii, grad_out_depth)
+        rs = ctx.raster_settings
+        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
+        z = lambda c: torch.zeros((c, rs.image_height, rs.image_width), device=means3D.device)
+        grad_out_color = z(3) if grad_out_color is None else grad_out_color
+        grad_out_depth = z(1) if grad_out_depth is None else grad_out_depth
+        (g_means2D, g_colors, _, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rot) = _C.rasterize_gaussians_backward_alpha(
+            rs.bg, means3D, radii, colors_precomp, None, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+            rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_out_depth, None, grad_alpha, sh, rs.sh_degree, rs.campos,
+            geom, ctx.num_rendered, binning, img, rs.debug)
+        return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rot, g_cov3D, None, None
+
+
+class _RasterizeGaussiansPairAlpha(torch.autograd.Function):
+    """_RasterizeGaussiansPair with the accumulated opacity as a fifth, differentiable output (see _RasterizeGaussiansAlpha)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                densify_accum=None, forward_only=False):
+        ctx.set_materialize_grads(False)      # see _RasterizeGaussiansAlpha
+        color, radii, depth, color2, img = _RasterizeGaussiansPair._forward(
+            ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+            densify_accum, forward_only)
+        rs = raster_settings
+        return color, radii, depth, color2, _C.raster_alpha(img, rs.image_height, rs.image_width)
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_color2, grad_alpha):
+        if grad_alpha is None:
+            return _RasterizeGaussiansPair.backward(ctx, grad_color, _grad_radii, grad_depth, grad_color2)
+        rs = ctx.raster_settings
+        colors_a, colors_b, means3D, scales, rotations, cov3Ds_precomp, radii, geom, binning, img = ctx.saved_tensors
+        z = lambda c: torch.zeros((c, rs.image_height, rs.image_width), device=means3D.device)
+        grad_color = z(3) if grad_color is None else grad_color
+        grad_depth = z(1) if grad_depth is None else grad_depth
+        grad_color2 = z(3) if grad_color2 is None else grad_color2
+        (g_means2D, g_col_a, g_col_b, g_opac, g_means3D, g_cov3D, _, g_scales, g_rot) = _C.rasterize_gaussians_backward_alpha(
+            rs.bg, means3D, radii, colors_a, colors_b, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+            rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_color2, grad_alpha, torch.Tensor([]), 0,
+            rs.campos, geom, ctx.num_rendered, binning, img, rs.debug, densify_accum=ctx.densify_accum)
         return g_means3D, g_means2D, g_col_a, g_col_b, g_opac, g_scales, g_rot, g_cov3D, None, None, None
 
 
@@ -161,13 +235,30 @@ class GaussianRasterizer(nn.Module):
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs)
 
+    def forward_alpha(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                      cov3D_precomp=None):
+        """Extension (not in the reference, whose rasterizer returns no accumulated opacity): `forward` plus the opacity image.
+        -> (color [3,H,W], radii [P], depth [1,H,W], alpha [1,H,W]); alpha = 1 - the final transmittance of the pixel, i.e. what
+        unit colours on a black background would render, and a loss on it back-propagates through the same backward pass."""
+        rs = self.raster_settings
+        if (shs is None) == (colors_precomp is None):
+            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+        has_sr = scales is not None or rotations is not None
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or (has_sr and cov3D_precomp is not None):
+            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        empty = torch.Tensor([])
+        n = lambda x: empty if x is None else x
+        tensors = (means3D, means2D, n(shs), n(colors_precomp), opacities, n(scales), n(rotations), n(cov3D_precomp))
+        return _RasterizeGaussiansAlpha.apply(*tensors, rs, _no_backward(*tensors))
+
     @torch.no_grad()
     def forward_decomposed(self, means3D, opacities, dynamic_mask, shs=None, colors_precomp=None, scales=None, rotations=None,
-                           cov3D_precomp=None):
+                           cov3D_precomp=None, with_alpha=False):
         """Extension for the evaluation path (gaussian_renderer/__init__.py:168-204, `return_decomposition=True`): the full
         render plus the dynamic-only and static-only renders, sharing ONE preprocess / binning / sort; the two subset images
         come from one extra blend pass and equal `self(...)` on the masked inputs bit for bit.  Inference only (no autograd).
-        -> dict(render, radii, depth, render_d, depth_d, render_s, depth_s)"""
+        -> dict(render, radii, depth, render_d, depth_d, render_s, depth_s); with_alpha adds alpha [1,H,W], the accumulated
+        opacity of the FULL render (forward_alpha)."""
         rs = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -181,21 +272,23 @@ class GaussianRasterizer(nn.Module):
             rs.bg, means3D, n(colors_precomp), opacities, n(scales), n(rotations), rs.scale_modifier, n(cov3D_precomp),
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, n(shs), rs.sh_degree,
             rs.campos, rs.prefiltered, rs.debug, allow_async=True, forward_only=True)
+        extra = dict(alpha=_C.raster_alpha(img, rs.image_height, rs.image_width)) if with_alpha else {}
         if P == 0:
             z3, z1 = torch.zeros_like(color), torch.zeros_like(depth)
-            return dict(render=color, radii=radii, depth=depth, render_d=z3, depth_d=z1, render_s=z3.clone(), depth_s=z1.clone())
+            return dict(render=color, radii=radii, depth=depth, render_d=z3, depth_d=z1, render_s=z3.clone(), depth_s=z1.clone(), **extra)
         cd, dd, cs, ds = _C.rasterize_decomposition(rs.bg, n(colors_precomp), dynamic_mask, rs.tanfovx, rs.tanfovy,
                                                     rs.image_height, rs.image_width, P, R, geom, binning, img, rs.debug)
-        return dict(render=color, radii=radii, depth=depth, render_d=cd, depth_d=dd, render_s=cs, depth_s=ds)
+        return dict(render=color, radii=radii, depth=depth, render_d=cd, depth_d=dd, render_s=cs, depth_s=ds, **extra)
 
     def forward_pair(self, means3D, means2D, opacities, colors_a, colors_b, scales=None, rotations=None, cov3D_precomp=None,
-                     densify_accum=None):
+                     densify_accum=None, with_alpha=False):
         """Extension (not in the reference): render the SAME Gaussians with two sets of precomputed colours, e.g. RGB and the
         feature head's output (gaussian_renderer/__init__.py:127-166 does this with two calls).
         -> (image_a [3,H,W], radii [P], depth [1,H,W], image_b [3,H,W]); gradients equal those of the two separate calls.
         densify_accum = (xyz_gradient_accum, denom, max_radii2D): the backward of this node also performs the reference's
         densification bookkeeping (train.py:489-493) in its per-Gaussian pass -- valid because this node yields the whole
-        viewspace gradient of the iteration."""
+        viewspace gradient of the iteration.
+        with_alpha=True appends the opacity image of forward_alpha: -> (image_a, radii, depth, image_b, alpha [1,H,W])."""
         has_sr = scales is not None or rotations is not None
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (has_sr and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
@@ -203,14 +296,16 @@ class GaussianRasterizer(nn.Module):
             # nothing to share / debug snapshots wanted: fall back to two ordinary nodes
             if densify_accum is not None:   # direct callers only: pipeline.render() decides before calling
                 raise RuntimeError("densify_accum needs the fused two-image node (P > 0, debug off)")
-            a, radii, depth = self.forward(means3D, means2D, opacities, colors_precomp=colors_a, scales=scales, rotations=rotations,
-                                           cov3D_precomp=cov3D_precomp)
+            first = self.forward_alpha if with_alpha else self.forward
+            a, radii, depth, *alpha = first(means3D, means2D, opacities, colors_precomp=colors_a, scales=scales, rotations=rotations,
+                                            cov3D_precomp=cov3D_precomp)
             b, _, _ = self.forward(means3D, means2D, opacities, colors_precomp=colors_b, scales=scales, rotations=rotations,
                                    cov3D_precomp=cov3D_precomp)
-            return a, radii, depth, b
+            return (a, radii, depth, b, *alpha)
         empty = torch.Tensor([])
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         tensors = (means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3D_precomp)
-        return _RasterizeGaussiansPair.apply(*tensors, self.raster_settings, densify_accum, _no_backward(*tensors))
+        node = _RasterizeGaussiansPairAlpha if with_alpha else _RasterizeGaussiansPair
+        return node.apply(*tensors, self.raster_settings, densify_accum, _no_backward(*tensors))
