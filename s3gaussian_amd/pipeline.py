@@ -434,6 +434,86 @@ class _LazyResult(dict):
         return other | dict(self)
 
 
+def _default_pipe(pipe: Optional[SimpleNamespace]) -> SimpleNamespace:
+    return pipe or SimpleNamespace(convert_SHs_python=True, compute_cov3D_python=False, debug=False)
+
+
+def _raster_settings(cam: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg: torch.Tensor, scale_modifier=1.0):
+    return GaussianRasterizationSettings(
+        image_height=int(cam["image_height"]), image_width=int(cam["image_width"]), tanfovx=cam["tanfovx"],
+        tanfovy=cam["tanfovy"], bg=bg, scale_modifier=scale_modifier, viewmatrix=cam["viewmatrix"],
+        projmatrix=cam["projmatrix"], sh_degree=pc.active_sh_degree, campos=cam["campos"], prefiltered=False,
+        debug=getattr(pipe, "debug", False))
+
+
+def _glue_route(pc: GaussianParams, pipe: SimpleNamespace, stage: str) -> bool:
+    """The fused glue (+ in a fine stage the fused deformation) route serves this model: GPU tensors, SH degree 3,
+    convert_SHs_python and fused_glue on (pipe.fused_glue=False: torch glue, tests), and in a fine stage a network on
+    Deformation._fused_any.  render() further asks for no override_color, render_views() for no compute_cov3D_python."""
+    return bool(pc.get_xyz.is_cuda and getattr(pipe, "convert_SHs_python", True) and pc.max_sh_degree == 3
+                and getattr(pipe, "fused_glue", True) and ("coarse" in stage or pc._deformation.deformation_net._fused_any()))
+
+
+def _deform_fused(pc: GaussianParams, t: float, stage: str, need_feat: bool, with_plane_reg: bool):
+    """The fused route's deformation of one timestamp -> (means3D_final, scales, rotations, opacity, dx, dshs, feat, plane_reg);
+    scales / rotations / opacity are still RAW (the glue kernel activates them) and in a coarse stage everything is the model's own.
+    By default only dx / dshs / feat come from the network (scales, rotations, opacity pass through, deformation.py:126-152) and
+    `shs + dshs` is folded into the glue kernel.  `time` is one timestamp repeated; with_plane_reg: the plane regulariser
+    (compute_regulation) rides on the sampler's node, so its gradient is the seed the sampler's backward accumulates onto."""
+    means3D, scales, rotations, opacity = pc.get_xyz, pc._scaling, pc._rotation, pc._opacity
+    if "coarse" in stage:
+        return means3D, scales, rotations, opacity, None, None, None, None
+    net = pc._deformation.deformation_net
+    hy = net.args
+    regw = (hy.time_smoothness_weight, hy.l1_time_planes, hy.plane_tv_weight) if with_plane_reg else None
+    heads = net.deform_heads(means3D, _uniform_time(float(t), means3D.device), uniform_time=True, reg_weights=regw, need_feat=need_feat,
+                             with_geometry=True)
+    dx, dshs, feat = heads[:3]
+    means3D_final = means3D if dx is None else means3D + dx     # dx is None: a static model (no_dx) has no position head
+    if heads[3] is not None:
+        # scale / rotation / opacity deformation (no_ds / no_dr / no_do off): the raw parameters plus the geometry heads' outputs
+        # go into the glue kernel in place of the raw ones (deformation.py:126-152, then the activations of :99-101)
+        scales, rotations, opacity = net.apply_geometry(scales, rotations, opacity, *heads[3])
+    return means3D_final, scales, rotations, opacity, dx, dshs, feat, heads[4] if with_plane_reg else None
+
+
+def _rasterize_view(rasterizer, means3D, means2D, opacity, scales, rotations, cov3D_precomp, shs, colors, want_feat, feat_colors,
+                    fused_pair, return_alpha, densify_accum=None):
+    """One view: the main render, then (want_feat) the feature render -- both from one node with fused_pair (RGB + feature image:
+    shared geometry forward, ONE fused backward, rasterizer.forward_pair), else the feature image from a plain node of its own.
+    -> (image, radii, depth, image2 | None, alpha | None)"""
+    geometry = dict(scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+    if want_feat and fused_pair:
+        image, radii, depth, image2, *alpha = rasterizer.forward_pair(
+            means3D=means3D, means2D=means2D, opacities=opacity, colors_a=colors, colors_b=feat_colors, densify_accum=densify_accum,
+            **geometry, **({"with_alpha": True} if return_alpha else {}))
+    else:
+        image, radii, depth, *alpha = (rasterizer.forward_alpha if return_alpha else rasterizer)(
+            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors, opacities=opacity, **geometry)
+        image2 = None
+        if want_feat:
+            image2, _, _ = rasterizer(means3D=means3D, means2D=means2D, shs=None, colors_precomp=feat_colors, opacities=opacity,
+                                      **geometry)
+    return image, radii, depth, image2, alpha[0] if alpha else None
+
+
+def _view_result(image, means2D, radii, depth, image2, alpha, want_feat, return_alpha, with_dx, dx, dshs, dshs_l1, plane_reg):
+    """The keys render() and render_views() share; which key appears when is the reference's (plus the extensions' "alpha",
+    "dshs_l1", "plane_reg")."""
+    out = _LazyResult({"render": image, "viewspace_points": means2D, "visibility_filter": radii > 0, "radii": radii, "depth": depth})
+    if want_feat:
+        out["feat"] = image2
+    if return_alpha:
+        out["alpha"] = alpha
+    if with_dx:
+        out.update({"dx": dx, "dshs": dshs})
+        if dshs_l1 is not None:
+            out["dshs_l1"] = dshs_l1
+    if plane_reg is not None:
+        out["plane_reg"] = plane_reg
+    return out
+
+
 def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torch.Tensor,
            scaling_modifier=1.0, override_color=None, stage="fine", return_decomposition=False, return_dx=False,
            render_feat=False, densify_accum=None, extra_colors=None, return_alpha=False):
@@ -458,43 +538,25 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
     screenspace_points = torch.empty_like(pc.get_xyz).requires_grad_(True)
     means3D = pc.get_xyz
     cam = viewpoint_camera
-    rs = GaussianRasterizationSettings(
-        image_height=int(cam["image_height"]), image_width=int(cam["image_width"]), tanfovx=cam["tanfovx"],
-        tanfovy=cam["tanfovy"], bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=cam["viewmatrix"],
-        projmatrix=cam["projmatrix"], sh_degree=pc.active_sh_degree, campos=cam["campos"], prefiltered=False,
-        debug=getattr(pipe, "debug", False))
+    rs = _raster_settings(cam, pc, pipe, bg_color, scaling_modifier)
     rasterizer = GaussianRasterizer(raster_settings=rs)
     time = None   # built where it is needed: [P,1] for the reference's module, ONE element for the fused sampler (uniform time)
     means2D = screenspace_points
     opacity = pc._opacity
     scales, rotations, cov3D_precomp = pc._scaling, pc._rotation, None
     dx = feat = dshs = shs_final = dshs_l1 = plane_reg = None
-    net = pc._deformation.deformation_net
-    hy = net.args
-    glue_ok = (means3D.is_cuda and override_color is None and getattr(pipe, "convert_SHs_python", True)
-               and pc.max_sh_degree == 3 and getattr(pipe, "fused_glue", True))   # pipe.fused_glue=False: torch glue (tests)
-    fused_glue = glue_ok and ("coarse" in stage or net._fused_any())
+    fused_glue = override_color is None and _glue_route(pc, pipe, stage)
     if "coarse" in stage:
         means3D_final, scales_final, rotations_final, opacity_final = means3D, scales, rotations, opacity
         if not fused_glue:
             shs_final = pc.get_features
     elif "fine" in stage:
         if fused_glue:
-            # default configuration: only dx / dshs / feat are produced by the network (scales, rotations, opacity pass
-            # through, deformation.py:126-152); `shs + dshs` is folded into the glue kernel below
-            # `time` is one timestamp repeated; under autograd the plane regulariser (compute_regulation) rides on the
-            # sampler's node so its gradient is the seed the sampler's backward accumulates onto
-            regw = ((hy.time_smoothness_weight, hy.l1_time_planes, hy.plane_tv_weight)
-                    if (stage == "fine" and torch.is_grad_enabled() and hy.time_smoothness_weight != 0) else None)
-            heads = net.deform_heads(means3D, _uniform_time(float(cam["time"]), dev), uniform_time=True, reg_weights=regw,
-                                     need_feat=render_feat or torch.is_grad_enabled(), with_geometry=True)
-            dx, dshs, feat = heads[:3]
-            plane_reg = heads[4] if regw is not None else None
-            means3D_final = means3D if dx is None else means3D + dx     # dx is None: a static model (no_dx) has no position head
-            if heads[3] is not None:
-                # scale / rotation / opacity deformation (no_ds / no_dr / no_do off): the raw parameters plus the geometry heads' outputs
-                # go into the glue kernel in place of the raw ones (deformation.py:126-152, then the activations of :99-101)
-                scales, rotations, opacity = net.apply_geometry(scales, rotations, opacity, *heads[3])
+            # under autograd the plane regulariser is a term of the fine stage's loss
+            hy = pc._deformation.deformation_net.args
+            means3D_final, scales, rotations, opacity, dx, dshs, feat, plane_reg = _deform_fused(
+                pc, cam["time"], stage, render_feat or torch.is_grad_enabled(),
+                stage == "fine" and torch.is_grad_enabled() and hy.time_smoothness_weight != 0)
             scales_final, rotations_final, opacity_final = scales, rotations, opacity
         else:
             time = torch.full((means3D.shape[0], 1), float(cam["time"]), device=dev)
@@ -545,34 +607,17 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
     # the bookkeeping rides in the pair node's backward only when that node really is the fused one (forward_pair falls back to
     # two ordinary nodes for P == 0 or debug snapshots); otherwise training_step runs the separate pass (optim.densify_stats)
     fuse_stats = bool(densify_accum is not None and pair and means3D_final.shape[0] > 0 and not rs.debug)
-    alpha = None
     if decomposed is not None:
-        rendered_image, radii, depth = decomposed["render"], decomposed["radii"], decomposed["depth"]
-        alpha = decomposed.get("alpha")
-    elif pair:
-        # RGB + feature image from one node: shared geometry forward, ONE fused backward (rasterizer.forward_pair)
-        rendered_image, radii, depth, rendered_image2, *alpha = rasterizer.forward_pair(
-            means3D=means3D_final, means2D=means2D, opacities=opacity, colors_a=colors_precomp, colors_b=feat,
-            scales=scales_final, rotations=rotations_final, cov3D_precomp=cov3D_precomp,
-            densify_accum=densify_accum if fuse_stats else None, **({"with_alpha": True} if return_alpha else {}))
-        alpha = alpha[0] if alpha else None
+        rendered_image, radii, depth, rendered_image2, alpha = (decomposed["render"], decomposed["radii"], decomposed["depth"], None,
+                                                                decomposed.get("alpha"))
     else:
-        rendered_image, radii, depth, *alpha = (rasterizer.forward_alpha if return_alpha else rasterizer)(
-            means3D=means3D_final, means2D=means2D, shs=shs_final, colors_precomp=colors_precomp, opacities=opacity,
-            scales=scales_final, rotations=rotations_final, cov3D_precomp=cov3D_precomp)
-        alpha = alpha[0] if alpha else None
-    out = _LazyResult({"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-                       "radii": radii, "depth": depth})
-    if return_alpha:
-        out["alpha"] = alpha
+        rendered_image, radii, depth, rendered_image2, alpha = _rasterize_view(
+            rasterizer, means3D_final, means2D, opacity, scales_final, rotations_final, cov3D_precomp, shs_final, colors_precomp,
+            want_feat, feat, pair, return_alpha, densify_accum if fuse_stats else None)
+    out = _view_result(rendered_image, screenspace_points, radii, depth, rendered_image2, alpha, want_feat, return_alpha,
+                       return_dx and "fine" in stage, dx, dshs, dshs_l1, plane_reg)
     if densify_accum is not None:
         out["densify_stats_fused"] = fuse_stats
-    if want_feat:
-        if not pair:
-            rendered_image2, _, _ = rasterizer(means3D=means3D_final, means2D=means2D, shs=None, colors_precomp=feat,
-                                               opacities=opacity, scales=scales_final, rotations=rotations_final,
-                                               cov3D_precomp=cov3D_precomp)
-        out["feat"] = rendered_image2
     if decomposed is not None:
         vis = out["visibility_filter"]
         out.update({"render_d": decomposed["render_d"], "depth_d": decomposed["depth_d"],
@@ -591,12 +636,6 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
                                        rotations=rotations_final[m] if rotations_final is not None else None,
                                        cov3D_precomp=cov3D_precomp[m] if cov3D_precomp is not None else None)
             out.update({f"render_{tag}": img, f"depth_{tag}": dep, f"visibility_filter_{tag}": rad > 0})
-    if return_dx and "fine" in stage:
-        out.update({"dx": dx, "dshs": dshs})
-        if dshs_l1 is not None:
-            out["dshs_l1"] = dshs_l1
-    if plane_reg is not None:
-        out["plane_reg"] = plane_reg
     if extra_colors is not None:
         P = means3D_final.shape[0]
         extra = []
@@ -710,9 +749,7 @@ def _fused_route(pc: GaussianParams, pipe: SimpleNamespace) -> bool:
     takes the route too, but produces no dx: nothing to colour a flow with or to split dynamic from static by): GPU tensors, the
     plain-grid network with any head configuration that has a position head (Deformation._fused_any: with or without the scale /
     rotation / opacity, SH and feature heads), SH degree 3, convert_SHs_python and fused_glue on."""
-    net = pc._deformation.deformation_net
-    return bool(pc.get_xyz.is_cuda and net._fused_any() and not net.args.no_dx and pc.max_sh_degree == 3
-                and getattr(pipe, "convert_SHs_python", True) and getattr(pipe, "fused_glue", True))
+    return _glue_route(pc, pipe, "fine") and not pc._deformation.deformation_net.args.no_dx
 
 
 def _fused_route_missing(pc: GaussianParams, pipe: SimpleNamespace) -> str:
@@ -1050,6 +1087,42 @@ def _sky_weight(opt, sky_mask) -> float:
     return float(getattr(opt, "lambda_sky", 0.0)) if sky_mask is not None else 0.0
 
 
+def _wanted_regularisers(hyper, opt, stage: str):
+    """-> (lambda_dx * mean|dx| wanted, lambda_dshs * mean|dshs| wanted, plane regulariser wanted)   (train.py:404-425)"""
+    fine = "fine" in stage
+    return (fine and not hyper.no_dx and opt.lambda_dx != 0, fine and not hyper.no_dshs and opt.lambda_dshs != 0,
+            stage == "fine" and hyper.time_smoothness_weight != 0)
+
+
+def _dshs_l1(pkg: Dict):
+    return pkg["dshs_l1"] if "dshs_l1" in pkg else torch.mean(torch.abs(pkg["dshs"]))
+
+
+def _plane_reg(pc: GaussianParams, pkgs, hyper):
+    """The plane regulariser a render has already evaluated on its sampler node, else evaluated here."""
+    reg = next((p["plane_reg"] for p in pkgs if p.get("plane_reg") is not None), None)
+    return reg if reg is not None else pc.compute_regulation(hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight)
+
+
+def _with_regularisers(pc: GaussianParams, loss, pkg: Dict, pkgs, sky_term, lam_sky: float, hyper, opt, stage: str):
+    """pixel-term loss + lambda_sky * sky_term (None: off) + the regularisers as ONE weighted node (_WeightedTerms): dx / dshs /
+    dshs_l1 from `pkg`, the plane regulariser from whichever of `pkgs` carries it."""
+    want_dx, want_dshs, want_reg = _wanted_regularisers(hyper, opt, stage)
+    terms, weights = [loss], [1.0]
+    if sky_term is not None:
+        terms.append(sky_term)
+        weights.append(lam_sky)
+    if want_dshs:
+        terms.append(_dshs_l1(pkg))
+        weights.append(float(opt.lambda_dshs))
+    if want_reg:
+        terms.append(_plane_reg(pc, pkgs, hyper))
+        weights.append(1.0)
+    if len(terms) == 1 and not want_dx:
+        return loss
+    return _WeightedTerms.apply(pkg["dx"] if want_dx else None, float(opt.lambda_dx), tuple(weights), *terms)
+
+
 def training_loss(pc: GaussianParams, pkg: Dict, gt_image, gt_depth, gt_feat, hyper, opt, stage="fine", fused_pixel_terms=True,
                   sky_mask=None):
     """train.py:395-425 for a batch of one view.  The per-pixel terms (L1, depth L2, DSSIM, feature L2) run as one fused
@@ -1059,51 +1132,45 @@ def training_loss(pc: GaussianParams, pkg: Dict, gt_image, gt_depth, gt_feat, hy
     lam_sky = _sky_weight(opt, sky_mask)
     if lam_sky != 0.0 and pkg.get("alpha") is None:
         raise RuntimeError('training_loss: the sky term needs pkg["alpha"]: render(..., return_alpha=True)')
-    fine = "fine" in stage
     use_feat = stage == "fine" and hyper.feat_head
     if fused_pixel_terms:
         loss = fused_photometric_loss(pkg["render"], gt_image[:3], pkg["depth"] if opt.lambda_depth != 0 else None, gt_depth,
                                       pkg["feat"] if use_feat else None, gt_feat, lambda_dssim=opt.lambda_dssim,
                                       lambda_depth=opt.lambda_depth, lambda_feat=opt.lambda_feat if use_feat else 0.0)
-    else:
-        image = pkg["render"].unsqueeze(0)
-        gt = gt_image.unsqueeze(0)
-        loss = l1_loss(image, gt[:, :3])
-        if opt.lambda_depth != 0:
-            loss = loss + compute_depth_l2(pkg["depth"].unsqueeze(0), gt_depth.unsqueeze(0)) * opt.lambda_depth
-        if opt.lambda_dssim != 0:
-            loss = loss + opt.lambda_dssim * (1.0 - fused_ssim(image, gt))
-        if use_feat:
-            loss = loss + l2_loss(pkg["feat"], gt_feat) * opt.lambda_feat
-    want_dx = fine and not hyper.no_dx and opt.lambda_dx != 0
-    want_dshs = fine and not hyper.no_dshs and opt.lambda_dshs != 0
-    want_reg = stage == "fine" and hyper.time_smoothness_weight != 0
-    if not fused_pixel_terms:    # the reference's own sequence, one term at a time
-        if want_dx:
-            loss = loss + torch.mean(torch.abs(pkg["dx"])) * opt.lambda_dx
-        if want_dshs:
-            dshs_l1 = pkg["dshs_l1"] if "dshs_l1" in pkg else torch.mean(torch.abs(pkg["dshs"]))
-            loss = loss + dshs_l1 * opt.lambda_dshs
-        if want_reg:
-            loss = loss + (pkg["plane_reg"] if pkg.get("plane_reg") is not None else
-                           pc.compute_regulation(hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight))
-        if lam_sky != 0.0:
-            loss = loss + _sky.sky_opacity_loss(pkg["alpha"], sky_mask, lam_sky)
-        return loss
-    terms, weights = [loss], [1.0]
-    if lam_sky != 0.0:
-        terms.append(_sky.sky_opacity_loss(pkg["alpha"], sky_mask, 1.0))
-        weights.append(lam_sky)
+        sky_term = _sky.sky_opacity_loss(pkg["alpha"], sky_mask, 1.0) if lam_sky != 0.0 else None
+        return _with_regularisers(pc, loss, pkg, [pkg], sky_term, lam_sky, hyper, opt, stage)
+    # the reference's own sequence, one term at a time
+    image = pkg["render"].unsqueeze(0)
+    gt = gt_image.unsqueeze(0)
+    loss = l1_loss(image, gt[:, :3])
+    if opt.lambda_depth != 0:
+        loss = loss + compute_depth_l2(pkg["depth"].unsqueeze(0), gt_depth.unsqueeze(0)) * opt.lambda_depth
+    if opt.lambda_dssim != 0:
+        loss = loss + opt.lambda_dssim * (1.0 - fused_ssim(image, gt))
+    if use_feat:
+        loss = loss + l2_loss(pkg["feat"], gt_feat) * opt.lambda_feat
+    want_dx, want_dshs, want_reg = _wanted_regularisers(hyper, opt, stage)
+    if want_dx:
+        loss = loss + torch.mean(torch.abs(pkg["dx"])) * opt.lambda_dx
     if want_dshs:
-        terms.append(pkg["dshs_l1"] if "dshs_l1" in pkg else torch.mean(torch.abs(pkg["dshs"])))
-        weights.append(float(opt.lambda_dshs))
+        loss = loss + _dshs_l1(pkg) * opt.lambda_dshs
     if want_reg:
-        terms.append(pkg["plane_reg"] if pkg.get("plane_reg") is not None else
-                     pc.compute_regulation(hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight))
-        weights.append(1.0)
-    if len(terms) == 1 and not want_dx:
-        return loss
-    return _WeightedTerms.apply(pkg["dx"] if want_dx else None, float(opt.lambda_dx), tuple(weights), *terms)
+        loss = loss + _plane_reg(pc, [pkg], hyper)
+    if lam_sky != 0.0:
+        loss = loss + _sky.sky_opacity_loss(pkg["alpha"], sky_mask, lam_sky)
+    return loss
+
+
+def _finish_step(pc: GaussianParams, pkgs, grad_hook, optimizer_step) -> None:
+    """What follows backward (and the densification statistics) in both steps: the caller's hook on the gradients, the optimizer
+    step -- `optimizer_step()` in place of `pc.optimizer.step()` where the caller brings one --, and the gradients cleared."""
+    if grad_hook is not None:
+        grad_hook(pc, pkgs)
+    if optimizer_step is not None:
+        optimizer_step()
+    else:
+        pc.optimizer.step()
+    pc.optimizer.zero_grad(set_to_none=True)
 
 
 def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hyper, opt, bg, stage="fine",
@@ -1119,7 +1186,7 @@ def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hy
     sky_mask with opt.lambda_sky != 0 (extension): the render also returns its opacity image and the loss gains
     lambda_sky * sky.sky_opacity_loss; its gradient rides in the same rasterizer backward, fused densify statistics included.
     Without a mask, or with lambda_sky = 0, nothing new is launched."""
-    pipe = pipe or SimpleNamespace(convert_SHs_python=True, compute_cov3D_python=False, debug=False)
+    pipe = _default_pipe(pipe)
     acc = (pc.xyz_gradient_accum, pc.denom, pc.max_radii2D) if densify_stats else None
     want_sky = _sky_weight(opt, sky_mask) != 0.0
     pkg = render(cam, pc, pipe, bg, stage=stage, return_dx=True, render_feat=(stage == "fine" and hyper.feat_head),
@@ -1132,13 +1199,7 @@ def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hy
         if vg is None:     # no gradient reached the screen-space points (nothing visible): the statistics do not move
             vg = torch.zeros_like(pkg["viewspace_points"])
         _densify_stats(pc.xyz_gradient_accum, pc.denom, pc.max_radii2D, vg, pkg["radii"])
-    if grad_hook is not None:
-        grad_hook(pc, pkg)
-    if optimizer_step is not None:
-        optimizer_step()
-    else:
-        pc.optimizer.step()
-    pc.optimizer.zero_grad(set_to_none=True)
+    _finish_step(pc, pkg, grad_hook, optimizer_step)
     return loss.detach(), pkg
 
 
@@ -1160,14 +1221,6 @@ def rig_batches(cameras, num_cams: int = 3):
     return out
 
 
-def _views_on_fused_route(pc: GaussianParams, pipe: SimpleNamespace, stage: str) -> bool:
-    """render()'s own condition for the fused glue (+ fused deformation) route, for the models render_views serves in one pass."""
-    net = pc._deformation.deformation_net
-    return bool(pc.get_xyz.is_cuda and getattr(pipe, "convert_SHs_python", True) and pc.max_sh_degree == 3
-                and getattr(pipe, "fused_glue", True) and not getattr(pipe, "compute_cov3D_python", False)
-                and ("coarse" in stage or net._fused_any()))
-
-
 def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation, return_alpha=False):
     """-> (result dicts, the skip word of each view's asynchronous forward or None)."""
     from . import raster_C
@@ -1179,7 +1232,7 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
     if "coarse" not in stage and "fine" not in stage:
         raise NotImplementedError
     dev = pc.get_xyz.device
-    if not _views_on_fused_route(pc, pipe, stage):
+    if not _glue_route(pc, pipe, stage) or getattr(pipe, "compute_cov3D_python", False):
         outs, words = [], []
         for cam, f in zip(cams, flags):     # the library route: nothing to share, the same results contract
             outs.append(render(cam, pc, pipe, bg_color, stage=stage, return_dx=return_dx, render_feat=f,
@@ -1190,28 +1243,15 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
     for i, cam in enumerate(cams):
         groups.setdefault(float(cam["time"]) if share_deformation else i, []).append(i)
     chunks = [idx[k:k + MAX_VIEWS] for idx in groups.values() for k in range(0, len(idx), MAX_VIEWS)]
-    net = pc._deformation.deformation_net
-    hy = net.args
+    hy = pc._deformation.deformation_net.args
     grad = torch.is_grad_enabled()
     outs, words = [None] * V, [None] * V
     for gi, idx in enumerate(chunks):
-        means3D = pc.get_xyz
-        scales, rotations, opacity = pc._scaling, pc._rotation, pc._opacity
-        dx = feat = dshs = plane_reg = None
-        if "coarse" in stage:
-            means3D_final = means3D
-        else:
-            # ONE evaluation of the field for the views of this timestamp; the plane regulariser is a term of the iteration, not of
-            # a view: it rides on the first group's sampler node only
-            regw = ((hy.time_smoothness_weight, hy.l1_time_planes, hy.plane_tv_weight)
-                    if (gi == 0 and stage == "fine" and grad and hy.time_smoothness_weight != 0) else None)
-            heads = net.deform_heads(means3D, _uniform_time(float(cams[idx[0]]["time"]), dev), uniform_time=True, reg_weights=regw,
-                                     need_feat=any(flags[i] for i in idx) or grad, with_geometry=True)
-            dx, dshs, feat = heads[:3]
-            plane_reg = heads[4] if regw is not None else None
-            means3D_final = means3D if dx is None else means3D + dx
-            if heads[3] is not None:
-                scales, rotations, opacity = net.apply_geometry(scales, rotations, opacity, *heads[3])
+        # ONE evaluation of the field for the views of this timestamp; the plane regulariser is a term of the iteration, not of
+        # a view: it rides on the first group's sampler node only
+        means3D_final, scales, rotations, opacity, dx, dshs, feat, plane_reg = _deform_fused(
+            pc, cams[idx[0]]["time"], stage, any(flags[i] for i in idx) or grad,
+            gi == 0 and stage == "fine" and grad and hy.time_smoothness_weight != 0)
         want_l1 = dshs is not None and grad
         glue_out = activations_and_colors_views(pc.active_sh_degree, pc._features_dc, pc._features_rest, dshs, pc.get_xyz,
                                                 torch.stack([cams[i]["campos"].reshape(3) for i in idx]), scales, rotations, opacity,
@@ -1219,43 +1259,16 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
         colors, scales_final, rotations_final, opacity_final = glue_out[:4]
         dshs_l1 = glue_out[4] if want_l1 else None
         for k, i in enumerate(idx):
-            cam = cams[i]
-            rs = GaussianRasterizationSettings(
-                image_height=int(cam["image_height"]), image_width=int(cam["image_width"]), tanfovx=cam["tanfovx"],
-                tanfovy=cam["tanfovy"], bg=bg_color, scale_modifier=1.0, viewmatrix=cam["viewmatrix"],
-                projmatrix=cam["projmatrix"], sh_degree=pc.active_sh_degree, campos=cam["campos"], prefiltered=False,
-                debug=getattr(pipe, "debug", False))
-            rasterizer = GaussianRasterizer(raster_settings=rs)
+            rasterizer = GaussianRasterizer(raster_settings=_raster_settings(cams[i], pc, pipe, bg_color))
             means2D = torch.empty_like(pc.get_xyz).requires_grad_(True)      # carries the viewspace gradient of THIS view (see render)
             want_feat = flags[i] and "fine" in stage
             # densify_accum is never handed over: a batch's statistics take the norm of the SUMMED viewspace gradient
-            if want_feat and getattr(pipe, "fused_pair", True):
-                image, radii, depth, image2, *alpha = rasterizer.forward_pair(
-                    means3D=means3D_final, means2D=means2D, opacities=opacity_final, colors_a=colors[k], colors_b=feat,
-                    scales=scales_final, rotations=rotations_final, cov3D_precomp=None, densify_accum=None,
-                    **({"with_alpha": True} if return_alpha else {}))
-            else:
-                image, radii, depth, *alpha = (rasterizer.forward_alpha if return_alpha else rasterizer)(
-                    means3D=means3D_final, means2D=means2D, shs=None, colors_precomp=colors[k], opacities=opacity_final,
-                    scales=scales_final, rotations=rotations_final, cov3D_precomp=None)
-                if want_feat:
-                    image2, _, _ = rasterizer(means3D=means3D_final, means2D=means2D, shs=None, colors_precomp=feat,
-                                              opacities=opacity_final, scales=scales_final, rotations=rotations_final,
-                                              cov3D_precomp=None)
+            image, radii, depth, image2, alpha = _rasterize_view(
+                rasterizer, means3D_final, means2D, opacity_final, scales_final, rotations_final, None, None, colors[k], want_feat, feat,
+                getattr(pipe, "fused_pair", True), return_alpha)
             words[i] = raster_C.async_skip_flag(dev)
-            out = _LazyResult({"render": image, "viewspace_points": means2D, "visibility_filter": radii > 0, "radii": radii,
-                               "depth": depth})
-            if want_feat:
-                out["feat"] = image2
-            if return_alpha:
-                out["alpha"] = alpha[0]
-            if return_dx and "fine" in stage:
-                out.update({"dx": dx, "dshs": dshs})
-                if dshs_l1 is not None:
-                    out["dshs_l1"] = dshs_l1
-            if plane_reg is not None:
-                out["plane_reg"] = plane_reg
-            outs[i] = out
+            outs[i] = _view_result(image, means2D, radii, depth, image2, alpha, want_feat, return_alpha, return_dx and "fine" in stage,
+                                   dx, dshs, dshs_l1, plane_reg)
     return outs, words
 
 
@@ -1320,26 +1333,8 @@ def training_loss_views(pc: GaussianParams, pkgs, gt_images, gt_depths, gt_feats
                                   [p["feat"] if s else None for p, s in zip(pkgs, sup)],
                                   [g if s else None for g, s in zip(gt_feats, sup)], lambda_dssim=opt.lambda_dssim,
                                   lambda_depth=opt.lambda_depth, lambda_feat=opt.lambda_feat if any(sup) else 0.0)
-    fine = "fine" in stage
-    last = pkgs[-1]
-    want_dx = fine and not hyper.no_dx and opt.lambda_dx != 0
-    want_dshs = fine and not hyper.no_dshs and opt.lambda_dshs != 0
-    want_reg = stage == "fine" and hyper.time_smoothness_weight != 0
-    terms, weights = [loss], [1.0]
-    if lam_sky != 0.0:
-        terms.append(_sky.sky_opacity_loss([p["alpha"] for p in pkgs], list(sky_masks), 1.0))
-        weights.append(lam_sky)
-    if want_dshs:
-        terms.append(last["dshs_l1"] if "dshs_l1" in last else torch.mean(torch.abs(last["dshs"])))
-        weights.append(float(opt.lambda_dshs))
-    if want_reg:
-        reg = next((p["plane_reg"] for p in pkgs if p.get("plane_reg") is not None), None)
-        terms.append(reg if reg is not None else
-                     pc.compute_regulation(hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight))
-        weights.append(1.0)
-    if len(terms) == 1 and not want_dx:
-        return loss
-    return _WeightedTerms.apply(last["dx"] if want_dx else None, float(opt.lambda_dx), tuple(weights), *terms)
+    sky_term = _sky.sky_opacity_loss([p["alpha"] for p in pkgs], list(sky_masks), 1.0) if lam_sky != 0.0 else None
+    return _with_regularisers(pc, loss, pkgs[-1], pkgs, sky_term, lam_sky, hyper, opt, stage)
 
 
 def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats, hyper, opt, bg, stage="fine",
@@ -1357,7 +1352,7 @@ def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats
     sky_masks (one per view) with opt.lambda_sky != 0: see training_loss_views; otherwise nothing new is launched."""
     from . import raster_C
     from .optim import densify_stats_views as _densify_stats_views
-    pipe = pipe or SimpleNamespace(convert_SHs_python=True, compute_cov3D_python=False, debug=False)
+    pipe = _default_pipe(pipe)
     cams = list(cams)
     V = len(cams)
     if V < 1 or len(gt_images) != V or (gt_depths is not None and len(gt_depths) != V) or (gt_feats is not None and len(gt_feats) != V):
@@ -1383,13 +1378,7 @@ def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats
         if V > 8:      # S3G_DENSIFY_MAX_VIEWS; a larger batch would need its gradients summed first -- not a rig's batch
             raise RuntimeError("training_step_views(densify_stats=True) serves batches of up to 8 views")
         _densify_stats_views(pc.xyz_gradient_accum, pc.denom, pc.max_radii2D, grads, [p["radii"] for p in pkgs])
-    if grad_hook is not None:
-        grad_hook(pc, pkgs)
-    if optimizer_step is not None:
-        optimizer_step()
-    else:
-        pc.optimizer.step()
-    pc.optimizer.zero_grad(set_to_none=True)
+    _finish_step(pc, pkgs, grad_hook, optimizer_step)
     return loss.detach(), pkgs
 
 

@@ -596,6 +596,74 @@ def _grad_slab(P: int, M: int, dev, internals: bool) -> dict:
     return views
 
 
+def _backward(background, means3D, radii, colors, colors2, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+              tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_color2, dL_dout_alpha, sh, degree, campos, geomBuffer, R,
+              binningBuffer, imageBuffer, debug, densify_accum, return_internals) -> dict:
+    """The one backward call behind the three entry points below.  colors2 / dL_dout_color2 (both or neither): the second image
+    of a two-image forward, which has no SH (`sh`, `degree` are then ignored).  dL_dout_alpha: an upstream gradient on the opacity
+    image.  Export: s3g_raster_backward_alpha if dL_dout_alpha is given, else s3g_raster_backward2[_accum] with colors2, else
+    s3g_raster_backward[_accum]; _accum iff densify_accum is given.
+    -> the gradient arrays by name, shaped: means2D, colors, colors2 (None for one image), opacity, means3D, cov3D, sh [P,M,3],
+    scales, rot, and with return_internals conic [P,2,2], depths [P,1]."""
+    L = _lib.lib()
+    dev = means3D.device
+    P = means3D.size(0)
+    H, W = dL_dout_color.size(1), dL_dout_color.size(2)
+    two = colors2 is not None
+    M = sh.size(1) if (not two and sh.numel() != 0) else 0
+    v = _grad_slab(P, M, dev, return_internals)
+    g_col2 = torch.empty((P, NUM_CHANNELS), dtype=torch.float32, device=dev) if two else None
+    if P != 0:
+        if dL_dout_alpha is not None and (tuple(dL_dout_alpha.shape[-2:]) != (H, W) or dL_dout_alpha.numel() != H * W):
+            raise RuntimeError(f"dL_dout_alpha must have {H} x {W} elements")
+        f32 = lambda t, name: None if t is None else _f32(t, name)
+        keep = [_f32(background, "bg"), _f32(means3D, "means3D"), None if two else _f32(sh, "sh"), _f32(colors, "colors_precomp"),
+                f32(colors2, "colors2"), _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3D_precomp, "cov3D_precomp"),
+                _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos"),
+                _f32(dL_dout_color, "dL_dout_color"), _f32(dL_dout_depth, "dL_dout_depth"),
+                f32(dL_dout_color2 if two else None, "dL_dout_color2"), f32(dL_dout_alpha, "dL_dout_alpha"), radii.contiguous()]
+        bg_, m3_, sh_, col_, col2_, sc_, rot_, cov_, view_, proj_, cam_, gcol_, gdep_, gcol2_, galpha_, radii_ = keep
+        inp = _inputs(P, 0 if two else degree, M, W, H, bg_, m3_, sh_, col_, None, sc_, scale_modifier, rot_, cov_, view_, proj_,
+                      tan_fovx, tan_fovy, cam_, False, debug)
+        nbytes = (L.s3g_raster_backward2_workspace_bytes if two else L.s3g_raster_backward_workspace_bytes)(P, int(R))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dens = C.byref(_densify_struct(densify_accum, P)) if densify_accum is not None else None
+        ptr = lambda t: _ptr(t) or None          # NULL for an absent tensor and for an array of no elements
+        arenas = (int(R), radii_.data_ptr(), ptr(geomBuffer), ptr(binningBuffer), ptr(imageBuffer), ptr(work), gcol_.data_ptr(),
+                  gdep_.data_ptr())
+        g = {k: ptr(t) for k, t in v.items()}
+        if galpha_ is not None:
+            fn = L.s3g_raster_backward_alpha
+            args = (C.byref(inp), ptr(col2_), *arenas, ptr(gcol2_), galpha_.data_ptr(), g["means2D"], g["conic"], g["opacity"],
+                    g["colors"], ptr(g_col2), g["depths"], g["means3D"], g["cov3D"], g["sh"], g["scales"], g["rot"], dens)
+        else:
+            if two:
+                fn = L.s3g_raster_backward2 if dens is None else L.s3g_raster_backward2_accum
+                args = (C.byref(inp), col2_.data_ptr(), *arenas, gcol2_.data_ptr(), g["means2D"], g["conic"], g["opacity"], g["colors"],
+                        g_col2.data_ptr(), g["depths"], g["means3D"], g["cov3D"], g["scales"], g["rot"])
+            else:
+                fn = L.s3g_raster_backward if dens is None else L.s3g_raster_backward_accum
+                args = (C.byref(inp), *arenas, g["means2D"], g["conic"], g["opacity"], g["colors"], g["depths"], g["means3D"],
+                        g["cov3D"], g["sh"], g["scales"], g["rot"])
+            if dens is not None:
+                args += (dens,)
+        with _lib.on_device(dev):
+            code = fn(*args, _lib.stream_ptr())
+        _lib.check(code)
+    elif two:
+        g_col2.zero_()
+    out = dict(means2D=v["means2D"].view(P, 3), colors=v["colors"].view(P, NUM_CHANNELS), colors2=g_col2, opacity=v["opacity"].view(P, 1),
+               means3D=v["means3D"].view(P, 3), cov3D=v["cov3D"].view(P, 6), sh=v["sh"].view(P, M, 3), scales=v["scales"].view(P, 3),
+               rot=v["rot"].view(P, 4))
+    if return_internals:
+        out.update(conic=v["conic"].view(P, 2, 2), depths=v["depths"].view(P, 1))
+    return out
+
+
+def _ordered(grads: dict, names, return_internals=False) -> tuple:
+    return tuple(grads[k] for k in names + (("conic", "depths") if return_internals else ()))
+
+
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, sh, degree,
                                  campos, geomBuffer, R, binningBuffer, imageBuffer, debug, return_internals=False,
@@ -603,38 +671,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     """-> (dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dsh[P,M,3],
            dL_dscales[P,3], dL_drotations[P,4])   (RAST/rasterize_points.cu:201).
     return_internals=True appends (dL_dconic[P,2,2], dL_ddepths[P,1]), the reference's internal intermediates."""
-    L = _lib.lib()
-    dev = means3D.device
-    P = means3D.size(0)
-    H, W = dL_dout_color.size(1), dL_dout_color.size(2)
-    M = sh.size(1) if sh.numel() != 0 else 0
-    v = _grad_slab(P, M, dev, return_internals)
-    if P != 0:
-        keep = [_f32(background, "bg"), _f32(means3D, "means3D"), _f32(sh, "sh"), _f32(colors, "colors_precomp"),
-                _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3D_precomp, "cov3D_precomp"),
-                _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos"),
-                _f32(dL_dout_color, "dL_dout_color"), _f32(dL_dout_depth, "dL_dout_depth"), radii.contiguous()]
-        bg_, m3_, sh_, col_, sc_, rot_, cov_, view_, proj_, cam_, gcol_, gdep_, radii_ = keep
-        inp = _inputs(P, degree, M, W, H, bg_, m3_, sh_, col_, None, sc_, scale_modifier, rot_, cov_, view_, proj_,
-                      tan_fovx, tan_fovy, cam_, False, debug)
-        work = torch.empty(L.s3g_raster_backward_workspace_bytes(P, int(R)), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            stream = _lib.stream_ptr()
-            args = (C.byref(inp), int(R), radii_.data_ptr(), _ptr(geomBuffer), _ptr(binningBuffer),
-                    _ptr(imageBuffer), _ptr(work), gcol_.data_ptr(), gdep_.data_ptr(),
-                    v["means2D"].data_ptr(), _ptr(v["conic"]), v["opacity"].data_ptr(),
-                    v["colors"].data_ptr(), _ptr(v["depths"]), v["means3D"].data_ptr(),
-                    v["cov3D"].data_ptr(), _ptr(v["sh"]), v["scales"].data_ptr(), v["rot"].data_ptr())
-            if densify_accum is None:
-                code = L.s3g_raster_backward(*args, stream)
-            else:
-                code = L.s3g_raster_backward_accum(*args, C.byref(_densify_struct(densify_accum, P)), stream)
-        _lib.check(code)
-    out = (v["means2D"].view(P, 3), v["colors"].view(P, NUM_CHANNELS), v["opacity"].view(P, 1), v["means3D"].view(P, 3),
-           v["cov3D"].view(P, 6), v["sh"].view(P, M, 3), v["scales"].view(P, 3), v["rot"].view(P, 4))
-    if return_internals:
-        out = out + (v["conic"].view(P, 2, 2), v["depths"].view(P, 1))
-    return out
+    grads = _backward(background, means3D, radii, colors, None, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                      projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, None, None, sh, degree, campos, geomBuffer, R,
+                      binningBuffer, imageBuffer, debug, densify_accum, return_internals)
+    return _ordered(grads, ("means2D", "colors", "opacity", "means3D", "cov3D", "sh", "scales", "rot"), return_internals)
 
 
 def rasterize_gaussians_backward2(background, means3D, radii, colors, colors2, scales, rotations, scale_modifier,
@@ -646,39 +686,10 @@ def rasterize_gaussians_backward2(background, means3D, radii, colors, colors2, s
     but the two colour gradients is the sum over both images.
     densify_accum = (xyz_gradient_accum [P,1], denom [P,1], max_radii2D [P]) float32: the per-Gaussian kernel also does the
     reference's add_densification_stats / max_radii2D update (s3g_raster_backward2_accum)."""
-    L = _lib.lib()
-    dev = means3D.device
-    P = means3D.size(0)
-    H, W = dL_dout_color.size(1), dL_dout_color.size(2)
-    v = _grad_slab(P, 0, dev, False)
-    g_col2 = torch.empty((P, NUM_CHANNELS), dtype=torch.float32, device=dev)
-    if P != 0:
-        keep = [_f32(background, "bg"), _f32(means3D, "means3D"), _f32(colors, "colors_precomp"), _f32(colors2, "colors2"),
-                _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3D_precomp, "cov3D_precomp"),
-                _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos"),
-                _f32(dL_dout_color, "dL_dout_color"), _f32(dL_dout_depth, "dL_dout_depth"),
-                _f32(dL_dout_color2, "dL_dout_color2"), radii.contiguous()]
-        bg_, m3_, col_, col2_, sc_, rot_, cov_, view_, proj_, cam_, gcol_, gdep_, gcol2_, radii_ = keep
-        inp = _inputs(P, 0, 0, W, H, bg_, m3_, None, col_, None, sc_, scale_modifier, rot_, cov_, view_, proj_,
-                      tan_fovx, tan_fovy, cam_, False, debug)
-        work = torch.empty(L.s3g_raster_backward2_workspace_bytes(P, int(R)), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            stream = _lib.stream_ptr()
-            args = (C.byref(inp), col2_.data_ptr(), int(R), radii_.data_ptr(), _ptr(geomBuffer),
-                    _ptr(binningBuffer), _ptr(imageBuffer), _ptr(work), gcol_.data_ptr(),
-                    gdep_.data_ptr(), gcol2_.data_ptr(), v["means2D"].data_ptr(), None,
-                    v["opacity"].data_ptr(), v["colors"].data_ptr(), g_col2.data_ptr(), None,
-                    v["means3D"].data_ptr(), v["cov3D"].data_ptr(), v["scales"].data_ptr(),
-                    v["rot"].data_ptr())
-            if densify_accum is None:
-                code = L.s3g_raster_backward2(*args, stream)
-            else:
-                code = L.s3g_raster_backward2_accum(*args, C.byref(_densify_struct(densify_accum, P)), stream)
-        _lib.check(code)
-    else:
-        g_col2.zero_()
-    return (v["means2D"].view(P, 3), v["colors"].view(P, NUM_CHANNELS), g_col2, v["opacity"].view(P, 1),
-            v["means3D"].view(P, 3), v["cov3D"].view(P, 6), v["scales"].view(P, 3), v["rot"].view(P, 4))
+    grads = _backward(background, means3D, radii, colors, colors2, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                      projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_color2, None, None, 0, campos, geomBuffer,
+                      R, binningBuffer, imageBuffer, debug, densify_accum, False)
+    return _ordered(grads, ("means2D", "colors", "colors2", "opacity", "means3D", "cov3D", "scales", "rot"))
 
 
 def raster_alpha(imageBuffer, image_height, image_width):
@@ -705,45 +716,10 @@ def rasterize_gaussians_backward_alpha(background, means3D, radii, colors, color
     dL_dout_alpha [1,H,W] on the opacity image as well (include/s3g_alpha.h::s3g_raster_backward_alpha).
     -> (dL_dmeans2D, dL_dcolors, dL_dcolors2 | None, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations);
     return_internals=True appends (dL_dconic[P,2,2], dL_ddepths[P,1]) like rasterize_gaussians_backward."""
-    L = _lib.lib()
-    dev = means3D.device
-    P = means3D.size(0)
-    H, W = dL_dout_color.size(1), dL_dout_color.size(2)
-    two = colors2 is not None
-    M = sh.size(1) if (not two and sh.numel() != 0) else 0
-    v = _grad_slab(P, M, dev, return_internals)
-    g_col2 = torch.empty((P, NUM_CHANNELS), dtype=torch.float32, device=dev) if two else None
-    if P != 0:
-        if tuple(dL_dout_alpha.shape[-2:]) != (H, W) or dL_dout_alpha.numel() != H * W:
-            raise RuntimeError(f"dL_dout_alpha must have {H} x {W} elements")
-        empty = torch.Tensor([])
-        keep = [_f32(background, "bg"), _f32(means3D, "means3D"), _f32(sh if not two else empty, "sh"),
-                _f32(colors, "colors_precomp"), _f32(colors2 if two else empty, "colors2"), _f32(scales, "scales"),
-                _f32(rotations, "rotations"), _f32(cov3D_precomp, "cov3D_precomp"), _f32(viewmatrix, "viewmatrix"),
-                _f32(projmatrix, "projmatrix"), _f32(campos, "campos"), _f32(dL_dout_color, "dL_dout_color"),
-                _f32(dL_dout_depth, "dL_dout_depth"), _f32(dL_dout_color2 if two else empty, "dL_dout_color2"),
-                _f32(dL_dout_alpha, "dL_dout_alpha"), radii.contiguous()]
-        bg_, m3_, sh_, col_, col2_, sc_, rot_, cov_, view_, proj_, cam_, gcol_, gdep_, gcol2_, galpha_, radii_ = keep
-        inp = _inputs(P, degree if not two else 0, M, W, H, bg_, m3_, sh_, col_, None, sc_, scale_modifier, rot_, cov_, view_,
-                      proj_, tan_fovx, tan_fovy, cam_, False, debug)
-        nbytes = (L.s3g_raster_backward2_workspace_bytes if two else L.s3g_raster_backward_workspace_bytes)(P, int(R))
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        dens = C.byref(_densify_struct(densify_accum, P)) if densify_accum is not None else None
-        with _lib.on_device(dev):
-            code = L.s3g_raster_backward_alpha(
-                C.byref(inp), _ptr(col2_) or None, int(R), radii_.data_ptr(), _ptr(geomBuffer), _ptr(binningBuffer),
-                _ptr(imageBuffer), _ptr(work), gcol_.data_ptr(), gdep_.data_ptr(), _ptr(gcol2_) or None, galpha_.data_ptr(),
-                v["means2D"].data_ptr(), _ptr(v["conic"]) or None, v["opacity"].data_ptr(), v["colors"].data_ptr(),
-                g_col2.data_ptr() if two else None, _ptr(v["depths"]) or None, v["means3D"].data_ptr(), v["cov3D"].data_ptr(), _ptr(v["sh"]) or None,
-                v["scales"].data_ptr(), v["rot"].data_ptr(), dens, _lib.stream_ptr())
-        _lib.check(code)
-    elif two:
-        g_col2.zero_()
-    out = (v["means2D"].view(P, 3), v["colors"].view(P, NUM_CHANNELS), g_col2, v["opacity"].view(P, 1), v["means3D"].view(P, 3),
-           v["cov3D"].view(P, 6), v["sh"].view(P, M, 3), v["scales"].view(P, 3), v["rot"].view(P, 4))
-    if return_internals:
-        out = out + (v["conic"].view(P, 2, 2), v["depths"].view(P, 1))
-    return out
+    grads = _backward(background, means3D, radii, colors, colors2, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                      projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_color2, dL_dout_alpha, sh, degree, campos,
+                      geomBuffer, R, binningBuffer, imageBuffer, debug, densify_accum, return_internals)
+    return _ordered(grads, ("means2D", "colors", "colors2", "opacity", "means3D", "cov3D", "sh", "scales", "rot"), return_internals)
 
 
 def _densify_struct(acc, P) -> _lib.DensifyAccum:

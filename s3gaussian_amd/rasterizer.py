@@ -33,19 +33,20 @@ def _snapshot(args):
     return tuple(a.detach().cpu().clone() if isinstance(a, torch.Tensor) else a for a in args)
 
 
+def _or_zero_images(grads, channels, rs, device):
+    """Output gradients with a zero image in place of each one that never arrived (an output that feeds no loss)."""
+    return [torch.zeros((c, rs.image_height, rs.image_width), device=device) if g is None else g for g, c in zip(grads, channels)]
+
+
 class _RasterizeGaussians(torch.autograd.Function):
-    """autograd node; forward keeps the three private arenas alive for backward (reference :44-156)."""
+    """autograd node; forward keeps the three private arenas alive for backward (reference :44-156).
+    with_alpha (extension): the accumulated opacity A = 1 - final_T as a fourth, differentiable output: one image-sized pass forward
+    (s3g_raster_alpha), and a backward that hands grad_alpha to the blend backward (s3g_raster_backward_alpha).  Without a gradient
+    on A -- or without with_alpha -- the backward is the reference's."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                forward_only=False):
-        return _RasterizeGaussians._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                            cov3Ds_precomp, raster_settings, forward_only)[:3]
-
-    @staticmethod
-    def _forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                 forward_only):
-        """-> (color, radii, depth, image arena): the body both single-image nodes share."""
+                forward_only=False, with_alpha=False):
         rs = raster_settings
         native_args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                        rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
@@ -66,49 +67,48 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.num_rendered = num_rendered
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
         ctx.mark_non_differentiable(radii)
-        return color, radii, depth, img
+        if not with_alpha:
+            return color, radii, depth
+        ctx.set_materialize_grads(False)      # an output that feeds no loss arrives as None in backward, not as a zero image
+        return color, radii, depth, _C.raster_alpha(img, rs.image_height, rs.image_width)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth):
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, grad_alpha=None):
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
-        if grad_out_color is None:
-            grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), device=means3D.device)
-        if grad_out_depth is None:
-            grad_out_depth = torch.zeros((1, rs.image_height, rs.image_width), device=means3D.device)
-        native_args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-                       rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_out_depth, sh,
-                       rs.sh_degree, rs.campos, geom, ctx.num_rendered, binning, img, rs.debug)
-        if rs.debug:
-            saved = _snapshot(native_args)
-            try:
+        grad_out_color, grad_out_depth = _or_zero_images((grad_out_color, grad_out_depth), (3, 1), rs, means3D.device)
+        if grad_alpha is None:
+            native_args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+                           rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_out_depth, sh,
+                           rs.sh_degree, rs.campos, geom, ctx.num_rendered, binning, img, rs.debug)
+            if rs.debug:
+                saved = _snapshot(native_args)
+                try:
+                    grads = _C.rasterize_gaussians_backward(*native_args)
+                except Exception:
+                    torch.save(saved, "snapshot_bw.dump")
+                    print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+                    raise
+            else:
                 grads = _C.rasterize_gaussians_backward(*native_args)
-            except Exception:
-                torch.save(saved, "snapshot_bw.dump")
-                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                raise
+            g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rot = grads
         else:
-            grads = _C.rasterize_gaussians_backward(*native_args)
-        g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rot = grads
-        # order of forward's inputs: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings
-        return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rot, g_cov3D, None, None
+            (g_means2D, g_colors, _, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rot) = _C.rasterize_gaussians_backward_alpha(
+                rs.bg, means3D, radii, colors_precomp, None, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+                rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_out_depth, None, grad_alpha, sh, rs.sh_degree, rs.campos,
+                geom, ctx.num_rendered, binning, img, rs.debug)
+        # order of forward's inputs: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, ...
+        return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rot, g_cov3D, None, None, None
 
 
 class _RasterizeGaussiansPair(torch.autograd.Function):
     """Two renders of one geometry (colours_a -> image + depth, colours_b -> second image) as ONE autograd node: one
     blend pass forward (s3g_raster_forward2) and one backward (s3g_raster_backward2) instead of two each, whose gradients
-    autograd would then add."""
+    autograd would then add.  with_alpha: the accumulated opacity as a fifth, differentiable output (see _RasterizeGaussians)."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                densify_accum=None, forward_only=False):
-        return _RasterizeGaussiansPair._forward(ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations,
-                                                cov3Ds_precomp, raster_settings, densify_accum, forward_only)[:4]
-
-    @staticmethod
-    def _forward(ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                 densify_accum, forward_only):
-        """-> (color, radii, depth, color2, image arena): the body both two-image nodes share."""
+                densify_accum=None, forward_only=False, with_alpha=False):
         rs = raster_settings
         empty = torch.Tensor([])
         common = (opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
@@ -120,81 +120,41 @@ class _RasterizeGaussiansPair(torch.autograd.Function):
         ctx.densify_accum = densify_accum
         ctx.save_for_backward(colors_a, colors_b, means3D, scales, rotations, cov3Ds_precomp, radii, geom, binning, img)
         ctx.mark_non_differentiable(radii)
-        return color, radii, depth, color2, img
-
-    @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_color2):
-        rs = ctx.raster_settings
-        colors_a, colors_b, means3D, scales, rotations, cov3Ds_precomp, radii, geom, binning, img = ctx.saved_tensors
-        z = lambda c: torch.zeros((c, rs.image_height, rs.image_width), device=means3D.device)
-        grad_color = z(3) if grad_color is None else grad_color
-        grad_depth = z(1) if grad_depth is None else grad_depth
-        grad_color2 = z(3) if grad_color2 is None else grad_color2
-        (g_means2D, g_col_a, g_col_b, g_opac, g_means3D, g_cov3D, g_scales, g_rot) = _C.rasterize_gaussians_backward2(
-            rs.bg, means3D, radii, colors_a, colors_b, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
-            rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_color2, rs.campos, geom, ctx.num_rendered,
-            binning, img, rs.debug, densify_accum=ctx.densify_accum)
-        return g_means3D, g_means2D, g_col_a, g_col_b, g_opac, g_scales, g_rot, g_cov3D, None, None, None
-
-
-class _RasterizeGaussiansAlpha(torch.autograd.Function):
-    """_RasterizeGaussians with the accumulated opacity A = 1 - final_T as a fourth, differentiable output: one image-sized
-    pass forward (s3g_raster_alpha), and a backward that hands grad_alpha to the blend backward (s3g_raster_backward_alpha).
-    Without a gradient on A the backward is _RasterizeGaussians' own."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                forward_only=False):
-        ctx.set_materialize_grads(False)      # an output that feeds no loss arrives as None in backward, not as a zero image
-        color, radii, depth, img = _RasterizeGaussians._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales,
-                                                                rotations, cov3Ds_precomp, raster_settings, forward_only)
-        rs = raster_settings
-        return color, radii, depth, _C.raster_alpha(img, rs.image_height, rs.image_width)
-
-    @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, grad_alpha):
-        if grad_alpha is None:
-            return _RasterizeGaussians.backward(ctx, grad_out_color, _grad_radii, grad_out_depth)
-        rs = ctx.raster_settings
-        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
-        z = lambda c: torch.zeros((c, rs.image_height, rs.image_width), device=means3D.device)
-        grad_out_color = z(3) if grad_out_color is None else grad_out_color
-        grad_out_depth = z(1) if grad_out_depth is None else grad_out_depth
-        (g_means2D, g_colors, _, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rot) = _C.rasterize_gaussians_backward_alpha(
-            rs.bg, means3D, radii, colors_precomp, None, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
-            rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_out_depth, None, grad_alpha, sh, rs.sh_degree, rs.campos,
-            geom, ctx.num_rendered, binning, img, rs.debug)
-        return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rot, g_cov3D, None, None
-
-
-class _RasterizeGaussiansPairAlpha(torch.autograd.Function):
-    """_RasterizeGaussiansPair with the accumulated opacity as a fifth, differentiable output (see _RasterizeGaussiansAlpha)."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                densify_accum=None, forward_only=False):
-        ctx.set_materialize_grads(False)      # see _RasterizeGaussiansAlpha
-        color, radii, depth, color2, img = _RasterizeGaussiansPair._forward(
-            ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-            densify_accum, forward_only)
-        rs = raster_settings
+        if not with_alpha:
+            return color, radii, depth, color2
+        ctx.set_materialize_grads(False)      # see _RasterizeGaussians
         return color, radii, depth, color2, _C.raster_alpha(img, rs.image_height, rs.image_width)
 
     @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_color2, grad_alpha):
-        if grad_alpha is None:
-            return _RasterizeGaussiansPair.backward(ctx, grad_color, _grad_radii, grad_depth, grad_color2)
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_color2, grad_alpha=None):
         rs = ctx.raster_settings
         colors_a, colors_b, means3D, scales, rotations, cov3Ds_precomp, radii, geom, binning, img = ctx.saved_tensors
-        z = lambda c: torch.zeros((c, rs.image_height, rs.image_width), device=means3D.device)
-        grad_color = z(3) if grad_color is None else grad_color
-        grad_depth = z(1) if grad_depth is None else grad_depth
-        grad_color2 = z(3) if grad_color2 is None else grad_color2
-        (g_means2D, g_col_a, g_col_b, g_opac, g_means3D, g_cov3D, _, g_scales, g_rot) = _C.rasterize_gaussians_backward_alpha(
-            rs.bg, means3D, radii, colors_a, colors_b, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
-            rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_color2, grad_alpha, torch.Tensor([]), 0,
-            rs.campos, geom, ctx.num_rendered, binning, img, rs.debug, densify_accum=ctx.densify_accum)
-        return g_means3D, g_means2D, g_col_a, g_col_b, g_opac, g_scales, g_rot, g_cov3D, None, None, None
+        grad_color, grad_depth, grad_color2 = _or_zero_images((grad_color, grad_depth, grad_color2), (3, 1, 3), rs, means3D.device)
+        head = (rs.bg, means3D, radii, colors_a, colors_b, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+                rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_color2)
+        tail = (rs.campos, geom, ctx.num_rendered, binning, img, rs.debug)
+        if grad_alpha is None:
+            (g_means2D, g_col_a, g_col_b, g_opac, g_means3D, g_cov3D, g_scales, g_rot) = _C.rasterize_gaussians_backward2(
+                *head, *tail, densify_accum=ctx.densify_accum)
+        else:
+            (g_means2D, g_col_a, g_col_b, g_opac, g_means3D, g_cov3D, _, g_scales, g_rot) = _C.rasterize_gaussians_backward_alpha(
+                *head, grad_alpha, torch.Tensor([]), 0, *tail, densify_accum=ctx.densify_accum)
+        return g_means3D, g_means2D, g_col_a, g_col_b, g_opac, g_scales, g_rot, g_cov3D, None, None, None, None
+
+
+def _check_arguments(scales, rotations, cov3D_precomp, colour_sources=None):
+    """The reference's two argument checks (:192-196), messages included.  colour_sources = (shs, colors_precomp), or None for an
+    entry point that takes precomputed colours only."""
+    if colour_sources is not None and (colour_sources[0] is None) == (colour_sources[1] is None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    has_sr = scales is not None or rotations is not None
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or (has_sr and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+
+
+def _or_empty(t):
+    """The reference's "not provided" sentinel: numel() == 0 -> NULL at the C ABI."""
+    return torch.Tensor([]) if t is None else t
 
 
 def _no_backward(*tensors) -> bool:
@@ -221,35 +181,19 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
-        rs = self.raster_settings
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        has_sr = scales is not None or rotations is not None
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or (has_sr and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        empty = torch.Tensor([])  # the reference's "not provided" sentinel: numel()==0 -> NULL at the C ABI
-        shs = empty if shs is None else shs
-        colors_precomp = empty if colors_precomp is None else colors_precomp
-        scales = empty if scales is None else scales
-        rotations = empty if rotations is None else rotations
-        cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-        return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs)
+        _check_arguments(scales, rotations, cov3D_precomp, colour_sources=(shs, colors_precomp))
+        return rasterize_gaussians(means3D, means2D, _or_empty(shs), _or_empty(colors_precomp), opacities, _or_empty(scales),
+                                   _or_empty(rotations), _or_empty(cov3D_precomp), self.raster_settings)
 
     def forward_alpha(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                       cov3D_precomp=None):
         """Extension (not in the reference, whose rasterizer returns no accumulated opacity): `forward` plus the opacity image.
         -> (color [3,H,W], radii [P], depth [1,H,W], alpha [1,H,W]); alpha = 1 - the final transmittance of the pixel, i.e. what
         unit colours on a black background would render, and a loss on it back-propagates through the same backward pass."""
-        rs = self.raster_settings
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        has_sr = scales is not None or rotations is not None
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or (has_sr and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        empty = torch.Tensor([])
-        n = lambda x: empty if x is None else x
-        tensors = (means3D, means2D, n(shs), n(colors_precomp), opacities, n(scales), n(rotations), n(cov3D_precomp))
-        return _RasterizeGaussiansAlpha.apply(*tensors, rs, _no_backward(*tensors))
+        _check_arguments(scales, rotations, cov3D_precomp, colour_sources=(shs, colors_precomp))
+        tensors = (means3D, means2D, _or_empty(shs), _or_empty(colors_precomp), opacities, _or_empty(scales), _or_empty(rotations),
+                   _or_empty(cov3D_precomp))
+        return _RasterizeGaussians.apply(*tensors, self.raster_settings, _no_backward(*tensors), True)
 
     @torch.no_grad()
     def forward_decomposed(self, means3D, opacities, dynamic_mask, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -260,13 +204,8 @@ class GaussianRasterizer(nn.Module):
         -> dict(render, radii, depth, render_d, depth_d, render_s, depth_s); with_alpha adds alpha [1,H,W], the accumulated
         opacity of the FULL render (forward_alpha)."""
         rs = self.raster_settings
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        has_sr = scales is not None or rotations is not None
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or (has_sr and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        e = torch.Tensor([])
-        n = lambda x: e if x is None else x
+        _check_arguments(scales, rotations, cov3D_precomp, colour_sources=(shs, colors_precomp))
+        n = _or_empty
         P = means3D.shape[0]
         R, color, depth, radii, geom, binning, img = _C.rasterize_gaussians(
             rs.bg, means3D, n(colors_precomp), opacities, n(scales), n(rotations), rs.scale_modifier, n(cov3D_precomp),
@@ -289,9 +228,7 @@ class GaussianRasterizer(nn.Module):
         densification bookkeeping (train.py:489-493) in its per-Gaussian pass -- valid because this node yields the whole
         viewspace gradient of the iteration.
         with_alpha=True appends the opacity image of forward_alpha: -> (image_a, radii, depth, image_b, alpha [1,H,W])."""
-        has_sr = scales is not None or rotations is not None
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or (has_sr and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        _check_arguments(scales, rotations, cov3D_precomp)
         if means3D.shape[0] == 0 or self.raster_settings.debug:
             # nothing to share / debug snapshots wanted: fall back to two ordinary nodes
             if densify_accum is not None:   # direct callers only: pipeline.render() decides before calling
@@ -302,10 +239,5 @@ class GaussianRasterizer(nn.Module):
             b, _, _ = self.forward(means3D, means2D, opacities, colors_precomp=colors_b, scales=scales, rotations=rotations,
                                    cov3D_precomp=cov3D_precomp)
             return (a, radii, depth, b, *alpha)
-        empty = torch.Tensor([])
-        scales = empty if scales is None else scales
-        rotations = empty if rotations is None else rotations
-        cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-        tensors = (means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3D_precomp)
-        node = _RasterizeGaussiansPairAlpha if with_alpha else _RasterizeGaussiansPair
-        return node.apply(*tensors, self.raster_settings, densify_accum, _no_backward(*tensors))
+        tensors = (means3D, means2D, colors_a, colors_b, opacities, _or_empty(scales), _or_empty(rotations), _or_empty(cov3D_precomp))
+        return _RasterizeGaussiansPair.apply(*tensors, self.raster_settings, densify_accum, _no_backward(*tensors), bool(with_alpha))

@@ -435,3 +435,49 @@ def test_single_image_entry_with_accumulators_internals_and_sh(gpu_device, name)
             err = rel_l2(got[idx].cpu().numpy(), want)
             print(f"alpha_errors scene={name} internal={key} new={err}")
             assert err <= GRAD_TOL, (key, err)
+
+
+def test_the_two_nodes_with_and_without_the_opacity_output(gpu_device):
+    """_RasterizeGaussians / _RasterizeGaussiansPair called directly: 3 / 4 outputs, one more with the trailing with_alpha=True; that
+    output is raster_alpha of a plain forward bit for bit, and with it left unused every input gradient is the plain node's."""
+    from s3gaussian_amd import raster_C as _C
+    from s3gaussian_amd.rasterizer import _RasterizeGaussians, _RasterizeGaussiansPair
+    dev = gpu_device
+    s = R.scene_a()
+    rs = settings_from(s, dev)
+    H, W = rs.image_height, rs.image_width
+    assert s["colors_precomp"].shape[1] == _C.NUM_CHANNELS
+    c, d, _, c2 = (u.to(dev) for u in _ups(H, W, "random"))
+    e = torch.Tensor([])
+
+    def run(pair, *trailing):
+        L = _leaves(s, dev)
+        if pair:
+            tensors = (L["means3D"], L["means2D"], L["colors_a"], L["colors_b"], L["opacities"], L["scales"], L["rotations"], e)
+            out = _RasterizeGaussiansPair.apply(*tensors, rs, *trailing)
+        else:
+            tensors = (L["means3D"], L["means2D"], e, L["colors_a"], L["opacities"], L["scales"], L["rotations"], e)
+            out = _RasterizeGaussians.apply(*tensors, rs, *trailing)
+        loss = (out[0] * c).sum() + (out[2] * d).sum()
+        if pair:
+            loss = loss + (out[3] * c2).sum()
+        loss.backward()                      # the opacity output, where there is one, feeds nothing
+        return out, L
+
+    img = _C.rasterize_gaussians(rs.bg, s["means3D"].to(dev), s["colors_precomp"].to(dev), s["opacities"].to(dev), s["scales"].to(dev),
+                                 s["rotations"].to(dev), 1.0, e, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, H, W, e, 0,
+                                 rs.campos, False, False)[6]
+    alpha = _C.raster_alpha(img, H, W)
+    assert 0.01 < float(alpha.mean()) < 0.999
+    for pair, n in ((False, 3), (True, 4)):
+        plain, Lp = run(pair)
+        assert len(plain) == n
+        with_alpha, La = run(pair, *((None,) if pair else ()), False, True)      # (densify_accum,) forward_only, with_alpha
+        assert len(with_alpha) == n + 1
+        assert torch.equal(with_alpha[-1], alpha)
+        for k in range(n):
+            assert torch.equal(with_alpha[k], plain[k]), k
+        for name in NAMES:
+            if name == "colors_b" and not pair:
+                continue
+            assert Lp[name].grad is not None and torch.equal(La[name].grad, Lp[name].grad), (pair, name)
