@@ -7,6 +7,9 @@
  *   s3g_photometric_forward / s3g_photometric_backward: the same two passes with the per-pixel terms of the training
  *       loss (s3g_pixel_losses_* below) folded in, so the image-space loss stage of a step is two launches + the combine.
  *
+ * Sources, one kernel family each: csrc/ssim.hip (s3g_ssim_*, s3g_photometric_*), csrc/pixel_loss.hip (s3g_pixel_losses_*,
+ * the combine included), csrc/plane_reg.hip (s3g_plane_regulation, s3g_scale_unless_one).
+ *
  * The window is separable.  A wave owns a strip of 64 columns x 21 rows of one channel and walks down its 31 input rows:
  * each row passes through a wave-private LDS row buffer for the horizontal 11-tap sums (no workgroup barrier), a register
  * ring of the last 11 rows of sums gives the vertical sums.  Forward keeps three per-pixel partial-derivative maps so

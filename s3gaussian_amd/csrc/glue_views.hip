@@ -2,8 +2,8 @@
 // and their gradients do not depend on the camera, only the view direction does.  One kernel each way reads f_dc / f_rest / dshs
 // once per Gaussian (421 B) and serves V cameras: V x 12 B of colours forward, V x 24 B backward, against V x ~440 B for V calls
 // of glue.hip.  Arithmetic per camera is glue.hip's, from the same source (glue_dev.hpp): colours are bit-identical to a
-// single-camera call, and with V = 1 so is every gradient.  The two other per-Gaussian / per-batch pieces of a multi-view
-// training step live here too: the densification statistics of a batch and the combine of a batch's loss accumulators.
+// single-camera call, and with V = 1 so is every gradient.  The other per-Gaussian piece of a multi-view training step lives
+// here too: the densification statistics of a batch.
 #include "glue_dev.hpp"
 
 #include "../../include/s3g_glue.h"
@@ -233,32 +233,6 @@ __global__ void __launch_bounds__(256) densify_stats_views_kernel(const StatsVie
   a.max_radii[i] = fmaxf(a.max_radii[i], (float)r);
 }
 
-// pixel_loss_combine_kernel (ssim.hip) for accumulators that V views added into: the image terms are means over n_views * 3 HW
-// elements, the feature term over n_feat_views * 3 HW (the reference supervises the last view's feature image only), the depth
-// term over the batch's joint count of valid pixels, which the accumulators already hold.
-__global__ void __launch_bounds__(64) pixel_loss_combine_views_kernel(const double* __restrict__ sums, double* __restrict__ totals,
-                                                                      int HW, int n_views, int n_feat_views, float w_l1,
-                                                                      float w_depth, float w_ssim, float w_feat,
-                                                                      float* __restrict__ loss) {
-  double T[5];
-#pragma unroll
-  for (int q = 0; q < 5; q++) {
-    double v = sums[(size_t)q * S3G_SUM_DOUBLES + threadIdx.x * S3G_SUM_STRIDE];   // S3G_SUM_SLOTS == 64 == one wave
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    T[q] = v;
-  }
-  if (threadIdx.x != 0) return;
-#pragma unroll
-  for (int q = 0; q < 5; q++) totals[q] = T[q];
-  const double N = 3.0 * (double)HW * (double)n_views, NF = 3.0 * (double)HW * (double)n_feat_views;
-  double v = 0.0;
-  if (w_l1 != 0.f) v += (double)w_l1 * T[1] / N;
-  if (w_depth != 0.f) v += (double)w_depth * T[2] / T[3];
-  if (w_ssim != 0.f) v += (double)w_ssim * (1.0 - T[0] / N);
-  if (w_feat != 0.f) v += (double)w_feat * T[4] / NF;
-  *loss = (float)v;
-}
-
 }  // namespace s3g
 
 using namespace s3g;
@@ -358,17 +332,4 @@ extern "C" int s3g_densify_stats_views_guarded(int P, int V, const float* const*
                                                float* xyz_gradient_accum, float* denom, float* max_radii2D,
                                                const uint32_t* skip_flag, void* stream_) {
   return densify_stats_views_impl(P, V, grad_xy, grad_stride, radii, xyz_gradient_accum, denom, max_radii2D, skip_flag, stream_);
-}
-
-extern "C" int s3g_pixel_losses_combine_views(int H, int W, int n_views, int n_feat_views, const double* sums, double* totals,
-                                              float w_l1, float w_depth, float w_ssim, float w_feat, float* loss, void* stream_) {
-  static_assert(S3G_SUM_SLOTS == 64, "the combine kernel reduces the slots with one wave");
-  if (H <= 0 || W <= 0 || n_views < 1 || n_feat_views < 0 || (n_feat_views == 0 && w_feat != 0.f) || !sums || !totals || !loss) {
-    set_error("s3g_pixel_losses_combine_views: bad argument");
-    return S3G_ERR_INVALID_ARG;
-  }
-  hipLaunchKernelGGL(pixel_loss_combine_views_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream_, sums, totals, H * W, n_views,
-                     n_feat_views, w_l1, w_depth, w_ssim, w_feat, loss);
-  S3G_HIP_CHECK(hipGetLastError());
-  return S3G_OK;
 }

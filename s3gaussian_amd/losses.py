@@ -16,6 +16,12 @@ _new_grad = torch.empty_like
 _new_maps = torch.empty
 
 
+class _PlaneRegDesc(C.Structure):
+    """struct s3g_plane_reg_desc (include/s3g_loss.h)."""
+    _fields_ = [("plane", C.c_void_p), ("grad", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("w_smooth", C.c_float),
+                ("w_l1", C.c_float)]
+
+
 def _bind():
     global _bound
     L = _lib.lib()
@@ -29,6 +35,8 @@ def _bind():
         L.s3g_pixel_losses_forward.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp]
         L.s3g_pixel_losses_combine.restype = C.c_int
         L.s3g_pixel_losses_combine.argtypes = [C.c_int, C.c_int, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp]
+        L.s3g_pixel_losses_combine_views.restype = C.c_int
+        L.s3g_pixel_losses_combine_views.argtypes = [C.c_int] * 4 + [vp] * 2 + [C.c_float] * 4 + [vp] * 2
         L.s3g_pixel_losses_backward.restype = C.c_int
         L.s3g_pixel_losses_backward.argtypes = ([C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, C.c_float,
                                                  C.c_float, C.c_float, vp, C.c_int, vp, vp, vp])
@@ -37,6 +45,8 @@ def _bind():
         L.s3g_photometric_backward.restype = C.c_int
         L.s3g_photometric_backward.argtypes = ([C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp,
                                                 C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp])
+        L.s3g_plane_regulation.restype = C.c_int
+        L.s3g_plane_regulation.argtypes = [C.c_int, C.POINTER(_PlaneRegDesc), vp, vp]
         _bound = True
     return L
 
@@ -81,130 +91,27 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11, size_ave
     return _SSIM.apply(img1, img2)
 
 
-class _PhotometricLoss(torch.autograd.Function):
-    """l1(image, gt) + w_depth * depth_l2 + w_ssim * (1 - ssim(image, gt)) + w_feat * l2(feat, gt_feat): with an SSIM term one
-    fused launch plus the 64-lane combine forward and one launch backward (include/s3g_loss.h::s3g_photometric_*); without it
-    the pixel-loss entry points."""
+class _PixelLoss(torch.autograd.Function):
+    """The per-pixel terms of train.py:389-425 over the concatenated batch of V >= 1 views of one H x W, as ONE node:
+        w_l1 * l1(images, gts) + w_depth * depth_l2(depths, gt_depths) + w_ssim * (1 - ssim(images, gts)) + w_feat * l2(feats, gt_feats)
+    `flat` is the six lists images, gt_images, depths, gt_depths, feats, gt_feats one after the other, V entries each, None where a
+    view has no such pair; the public functions below validate them and decide which pairs take part.  The images may be absent
+    only when w_ssim == 0.  With an SSIM term: V fused strip-walking launches ADD into one set of accumulators, one 64-lane combine,
+    V backward launches (include/s3g_loss.h::s3g_photometric_*); without it the pixel-loss entry points (s3g_pixel_losses_*).  L1
+    and SSIM are means over V*3*H*W, the depth term over the batch's joint count of valid pixels, the feature term over the views
+    that have one."""
 
     @staticmethod
-    def forward(ctx, image, gt_image, depth, gt_depth, feat, gt_feat, w_ssim, w_depth, w_feat, max_depth):
-        if not image.is_cuda:
-            raise RuntimeError(f"photometric_loss: images must live on the GPU (got {image.device}); no CPU fallback")
+    def forward(ctx, H, W, w_l1, w_ssim, w_depth, w_feat, max_depth, *flat):
         L = _bind()
+        V = len(flat) // 6
+        w_l1, w_ssim, w_depth, w_feat, max_depth = float(w_l1), float(w_ssim), float(w_depth), float(w_feat), float(max_depth)
         c = lambda t: None if t is None else t.detach().contiguous().float()
-        img, gt = c(image), c(gt_image)
-        if img.dim() != 3 or img.shape[0] != 3 or gt.shape != img.shape:
-            raise RuntimeError("photometric_loss expects image and gt_image of shape [3,H,W]")
-        _, H, W = img.shape
-        dev = img.device
-        w_ssim, w_depth, w_feat = float(w_ssim), float(w_depth), float(w_feat)
-        dep, gdep = (c(depth), c(gt_depth)) if (depth is not None and w_depth != 0.0) else (None, None)
-        ft, gft = (c(feat), c(gt_feat)) if (feat is not None and w_feat != 0.0) else (None, None)
-        for a, b, n in ((dep, gdep, H * W), (ft, gft, 3 * H * W)):
-            if a is not None and (a.numel() != n or b.numel() != n):
-                raise RuntimeError("photometric_loss: depth must have H*W and feat 3*H*W elements, like their targets")
-        sums = torch.zeros(5 * SUM_DOUBLES + 5, dtype=torch.float64, device=dev)   # 5 accumulators + their 5 totals
-        totals = sums[5 * SUM_DOUBLES:]
-        maps = _new_maps((3, 3, H, W), dtype=torch.float32, device=dev) if w_ssim != 0.0 else None
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        p = lambda t: None if t is None else t.data_ptr()
-        with _lib.on_device(dev):
-            st = _lib.stream_ptr()
-            if maps is not None:
-                _lib.check(L.s3g_photometric_forward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), float(max_depth),
-                                                     p(sums), p(maps[0]), p(maps[1]), p(maps[2]), st))
-            else:
-                _lib.check(L.s3g_pixel_losses_forward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), float(max_depth),
-                                                      p(sums), st))
-            _lib.check(L.s3g_pixel_losses_combine(H, W, p(sums), p(totals), 1.0, w_depth if dep is not None else 0.0, w_ssim,
-                                                  w_feat if ft is not None else 0.0, p(loss), st))
-        ctx.save_for_backward(img, gt, *(t for t in (dep, gdep, ft, gft, maps) if t is not None), totals)
-        ctx.cfg = (H, W, dep is not None, ft is not None, maps is not None, w_ssim, w_depth, w_feat, float(max_depth),
-                   None if depth is None else depth.shape, None if feat is None else feat.shape, image.shape)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        H, W, has_d, has_f, has_s, w_ssim, w_depth, w_feat, max_depth, dshape, fshape, ishape = ctx.cfg
-        saved = list(ctx.saved_tensors)
-        img, gt = saved[0], saved[1]
-        k = 2
-        dep = gdep = ft = gft = maps = None
-        if has_d:
-            dep, gdep = saved[k], saved[k + 1]
-            k += 2
-        if has_f:
-            ft, gft = saved[k], saved[k + 1]
-            k += 2
-        if has_s:
-            maps = saved[k]
-            k += 1
-        sums = saved[k]
-        L = _bind()
-        dev = img.device
-        g = g.detach().reshape(1).contiguous().float()
-        g_img = _new_grad(img)
-        g_dep = _new_grad(dep) if has_d else None
-        g_ft = _new_grad(ft) if has_f else None
-        p = lambda t: None if t is None else t.data_ptr()
-        with _lib.on_device(dev):
-            st = _lib.stream_ptr()
-            if has_s:
-                _lib.check(L.s3g_photometric_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(maps[0]),
-                                                      p(maps[1]), p(maps[2]), p(sums), p(g), w_ssim, 1.0, w_depth, w_feat,
-                                                      p(g_img), p(g_dep), p(g_ft), st))
-            else:
-                _lib.check(L.s3g_pixel_losses_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(sums),
-                                                       p(g), 1.0, w_depth, w_feat, p(g_img), 0, p(g_dep), p(g_ft), st))
-        return (g_img.view(ishape), None, g_dep.view(dshape) if has_d else None, None,
-                g_ft.view(fshape) if has_f else None, None, None, None, None, None)
-
-
-def photometric_loss(image, gt_image, depth=None, gt_depth=None, feat=None, gt_feat=None, lambda_dssim=0.0,
-                     lambda_depth=0.0, lambda_feat=0.0, max_depth=80.0):
-    """The per-pixel part of train.py:395-425 for one view:
-        l1_loss(image, gt_image) + lambda_depth * compute_depth("l2", depth, gt_depth)
-        + lambda_dssim * (1 - ssim(image, gt_image)) + lambda_feat * l2_loss(feat, gt_feat)
-    image/gt_image/feat/gt_feat [3,H,W], depth/gt_depth [1,H,W] or [H,W]; a zero weight (or a missing pair) skips a term."""
-    return _PhotometricLoss.apply(image, gt_image, depth, gt_depth, feat, gt_feat, lambda_dssim, lambda_depth, lambda_feat,
-                                  max_depth)
-
-
-class _PhotometricLossViews(torch.autograd.Function):
-    """_PhotometricLoss over the concatenated batch of V views of one H x W (train.py:389-425): V forward launches ADD into one
-    set of accumulators, one combine (include/s3g_loss.h::s3g_pixel_losses_combine_views), V backward launches.  L1 and SSIM are
-    means over V*3*H*W, the depth term over the batch's joint count of valid pixels, the feature term over the views that have one."""
-
-    @staticmethod
-    def forward(ctx, V, w_ssim, w_depth, w_feat, max_depth, *flat):
-        images, gts, depths, gt_depths, feats, gt_feats = (list(flat[k * V:(k + 1) * V]) for k in range(6))
-        if not images[0].is_cuda:
-            raise RuntimeError(f"photometric_loss_views: images must live on the GPU (got {images[0].device}); no CPU fallback")
-        L = _bind()
-        L.s3g_pixel_losses_combine_views.restype = C.c_int
-        L.s3g_pixel_losses_combine_views.argtypes = ([C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_float] * 4 + [C.c_void_p] * 2)
-        c = lambda t: None if t is None else t.detach().contiguous().float()
-        w_ssim, w_depth, w_feat, max_depth = float(w_ssim), float(w_depth), float(w_feat), float(max_depth)
-        _, H, W = images[0].shape
-        dev = images[0].device
-        views = []
-        for v in range(V):
-            img, gt = c(images[v]), c(gts[v])
-            if img.dim() != 3 or img.shape[0] != 3 or gt.shape != img.shape:
-                raise RuntimeError(f"photometric_loss_views: view {v}: image and gt_image must be [3,H,W] (got {tuple(img.shape)}, "
-                                   f"{tuple(gt.shape)})")
-            if tuple(img.shape[1:]) != (H, W):
-                raise RuntimeError(f"photometric_loss_views: view {v} is {img.shape[1]}x{img.shape[2]}, view 0 is {H}x{W}: "
-                                   "all views of a batch must have one size")
-            dep, gdep = (c(depths[v]), c(gt_depths[v])) if (depths[v] is not None and w_depth != 0.0) else (None, None)
-            ft, gft = (c(feats[v]), c(gt_feats[v])) if (feats[v] is not None and w_feat != 0.0) else (None, None)
-            for a, b, n in ((dep, gdep, H * W), (ft, gft, 3 * H * W)):
-                if a is not None and (b is None or a.numel() != n or b.numel() != n):
-                    raise RuntimeError(f"photometric_loss_views: view {v}: depth must have H*W and feat 3*H*W elements, like "
-                                       "their targets")
-            views.append((img, gt, dep, gdep, ft, gft))
-        n_feat = sum(1 for vw in views if vw[4] is not None)
+        views = [tuple(c(flat[k * V + v]) for k in range(6)) for v in range(V)]   # (img, gt, dep, gdep, ft, gft) per view
+        dev = next(t for t in views[0] if t is not None).device
+        has_image = views[0][0] is not None
         any_depth = any(vw[2] is not None for vw in views)
+        n_feat = sum(1 for vw in views if vw[4] is not None)
         sums = torch.zeros(5 * SUM_DOUBLES + 5, dtype=torch.float64, device=dev)   # 5 accumulators + their 5 totals
         totals = sums[5 * SUM_DOUBLES:]
         maps = [_new_maps((3, 3, H, W), dtype=torch.float32, device=dev) for _ in range(V)] if w_ssim != 0.0 else None
@@ -220,18 +127,20 @@ class _PhotometricLossViews(torch.autograd.Function):
                 else:
                     _lib.check(L.s3g_pixel_losses_forward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth,
                                                           p(sums), st))
-            _lib.check(L.s3g_pixel_losses_combine_views(H, W, V, n_feat, p(sums), p(totals), 1.0, w_depth if any_depth else 0.0,
-                                                        w_ssim, w_feat if n_feat else 0.0, p(loss), st))
+            _lib.check(L.s3g_pixel_losses_combine_views(H, W, V, n_feat, p(sums), p(totals), w_l1 if has_image else 0.0,
+                                                        w_depth if any_depth else 0.0, w_ssim, w_feat if n_feat else 0.0,
+                                                        p(loss), st))
         ctx.save_for_backward(*(t for vw in views for t in vw if t is not None), *(maps or ()), totals)
         ctx.present = [[t is not None for t in vw] for vw in views]
-        ctx.cfg = (V, H, W, n_feat, w_ssim, w_depth, w_feat, max_depth)
-        ctx.shapes = [tuple(None if t is None else t.shape for t in (images[v], depths[v], feats[v])) for v in range(V)]
+        ctx.cfg = (H, W, n_feat, w_l1, w_ssim, w_depth, w_feat, max_depth)
+        ctx.shapes = [None if t is None else t.shape for t in flat]
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        V, H, W, n_feat, w_ssim, w_depth, w_feat, max_depth = ctx.cfg
+        H, W, n_feat, w_l1, w_ssim, w_depth, w_feat, max_depth = ctx.cfg
         L = _bind()
+        V = len(ctx.present)
         saved = iter(ctx.saved_tensors)
         views = [tuple(next(saved) if there else None for there in row) for row in ctx.present]
         maps = [next(saved) for _ in range(V)] if w_ssim != 0.0 else None
@@ -239,15 +148,17 @@ class _PhotometricLossViews(torch.autograd.Function):
         g = g.detach().reshape(1).contiguous().float()
         # the kernels divide by this view's 3*H*W: the batch means take 1/V (1/n_feat) more.  The depth weight stays whole:
         # totals[3], which the kernels divide by, already is the joint count
-        w_l1_v, w_ssim_v, w_feat_v = 1.0 / V, w_ssim / V, (w_feat / n_feat if n_feat else 0.0)
+        w_l1_v, w_ssim_v, w_feat_v = w_l1 / V, w_ssim / V, (w_feat / n_feat if n_feat else 0.0)
+        need = ctx.needs_input_grad[7:]
         p = lambda t: None if t is None else t.data_ptr()
-        g_imgs, g_deps, g_fts = [], [], []
+        grads = [None] * (6 * V)
         with _lib.on_device(totals.device):
             st = _lib.stream_ptr()
             for v, (img, gt, dep, gdep, ft, gft) in enumerate(views):
-                g_img = _new_grad(img)
-                g_dep = _new_grad(dep) if dep is not None else None
-                g_ft = _new_grad(ft) if ft is not None else None
+                # a gradient nobody asked for is not formed, except the image's on the SSIM route, whose entry point requires it
+                g_img = _new_grad(img) if img is not None and (maps is not None or need[v]) else None
+                g_dep = _new_grad(dep) if dep is not None and need[2 * V + v] else None
+                g_ft = _new_grad(ft) if ft is not None and need[4 * V + v] else None
                 if maps is not None:
                     m = maps[v]
                     _lib.check(L.s3g_photometric_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(m[0]),
@@ -256,12 +167,55 @@ class _PhotometricLossViews(torch.autograd.Function):
                 else:
                     _lib.check(L.s3g_pixel_losses_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(totals),
                                                            p(g), w_l1_v, w_depth, w_feat_v, p(g_img), 0, p(g_dep), p(g_ft), st))
-                ishape, dshape, fshape = ctx.shapes[v]
-                g_imgs.append(g_img.view(ishape))
-                g_deps.append(None if g_dep is None else g_dep.view(dshape))
-                g_fts.append(None if g_ft is None else g_ft.view(fshape))
-        none = [None] * V
-        return (None, None, None, None, None, *g_imgs, *none, *g_deps, *none, *g_fts, *none)
+                for k, t in ((0, g_img), (2, g_dep), (4, g_ft)):
+                    if t is not None:
+                        grads[k * V + v] = t.view(ctx.shapes[k * V + v])   # the caller's shape
+        return (None,) * 7 + tuple(grads)
+
+
+def _require_gpu(name, t):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: images must live on the GPU (got {t.device}); no CPU fallback")
+
+
+def _require_pairs(name, pairs):
+    for what, a, b, n in pairs:
+        if (a is None) != (b is None) or (a is not None and (a.numel() != n or b.numel() != n)):
+            raise RuntimeError(f"{name}: {what} and its target must both be given, {n} elements each")
+
+
+def _photometric(name, images, gt_images, depths, gt_depths, feats, gt_feats, w_ssim, w_depth, w_feat, max_depth):
+    """photometric_loss / photometric_loss_views: [3,H,W] images of one size; a depth or feature pair takes part when its weight is
+    not 0 and its prediction is there."""
+    V = len(images)
+    _require_gpu(name, images[0])
+    w_depth, w_feat = float(w_depth), float(w_feat)
+    depths, gt_depths, feats, gt_feats = list(depths), list(gt_depths), list(feats), list(gt_feats)
+    for v, (img, gt) in enumerate(zip(images, gt_images)):
+        if img.dim() != 3 or img.shape[0] != 3 or gt.shape != img.shape:
+            raise RuntimeError(f"{name}: view {v}: image and gt_image must be [3,H,W] (got {tuple(img.shape)}, {tuple(gt.shape)})")
+        if v == 0:
+            _, H, W = img.shape
+        elif tuple(img.shape[1:]) != (H, W):
+            raise RuntimeError(f"{name}: view {v} is {img.shape[1]}x{img.shape[2]}, view 0 is {H}x{W}: all views of a batch must "
+                               "have one size")
+        if depths[v] is None or w_depth == 0.0:
+            depths[v] = gt_depths[v] = None
+        if feats[v] is None or w_feat == 0.0:
+            feats[v] = gt_feats[v] = None
+        _require_pairs(f"{name}: view {v}", (("depth", depths[v], gt_depths[v], H * W), ("feat", feats[v], gt_feats[v], 3 * H * W)))
+    return _PixelLoss.apply(H, W, 1.0, w_ssim, w_depth, w_feat, max_depth, *images, *gt_images, *depths, *gt_depths, *feats,
+                            *gt_feats)
+
+
+def photometric_loss(image, gt_image, depth=None, gt_depth=None, feat=None, gt_feat=None, lambda_dssim=0.0,
+                     lambda_depth=0.0, lambda_feat=0.0, max_depth=80.0):
+    """The per-pixel part of train.py:395-425 for one view:
+        l1_loss(image, gt_image) + lambda_depth * compute_depth("l2", depth, gt_depth)
+        + lambda_dssim * (1 - ssim(image, gt_image)) + lambda_feat * l2_loss(feat, gt_feat)
+    image/gt_image/feat/gt_feat [3,H,W], depth/gt_depth [1,H,W] or [H,W]; a zero weight (or a missing pair) skips a term."""
+    return _photometric("photometric_loss", [image], [gt_image], [depth], [gt_depth], [feat], [gt_feat], lambda_dssim,
+                        lambda_depth, lambda_feat, max_depth)
 
 
 def photometric_loss_views(images, gt_images, depths=None, gt_depths=None, feats=None, gt_feats=None, lambda_dssim=0.0,
@@ -276,116 +230,54 @@ def photometric_loss_views(images, gt_images, depths=None, gt_depths=None, feats
     V = len(images)
     if V < 1:
         raise RuntimeError("photometric_loss_views: no views")
-    none = [None] * V
-    lists = [list(images), list(gt_images), list(depths) if depths is not None else none,
-             list(gt_depths) if gt_depths is not None else none, list(feats) if feats is not None else none,
-             list(gt_feats) if gt_feats is not None else none]
+    lists = [[None] * V if l is None else list(l) for l in (images, gt_images, depths, gt_depths, feats, gt_feats)]
     for name, l in zip(("images", "gt_images", "depths", "gt_depths", "feats", "gt_feats"), lists):
         if len(l) != V:
             raise RuntimeError(f"photometric_loss_views: {name} has {len(l)} entries for {V} views")
-    flat = [t for l in lists for t in l]
-    return _PhotometricLossViews.apply(V, lambda_dssim, lambda_depth, lambda_feat, max_depth, *flat)
-
-
-class _PixelTerms(torch.autograd.Function):
-    """w_l1 * l1(image, gt) + w_depth * depth_l2(depth, gt_depth) + w_feat * l2(feat, gt_feat) with any subset of the three
-    pairs present: one kernel forward (+ the 64-lane combine), one backward (include/s3g_loss.h::s3g_pixel_losses_*).  The
-    zero-edit route (s3gaussian_amd.patch) calls it once per term, because train.py:395-425 adds them one function call at a
-    time; photometric_loss above is the all-in-one form."""
-
-    @staticmethod
-    def forward(ctx, image, gt_image, depth, gt_depth, feat, gt_feat, w_l1, w_depth, w_feat, max_depth):
-        first = next(t for t in (image, depth, feat) if t is not None)
-        if not first.is_cuda:
-            raise RuntimeError(f"pixel_terms: images must live on the GPU (got {first.device}); no CPU fallback")
-        L = _bind()
-        c = lambda t: None if t is None else t.detach().contiguous().float()
-        img, gt, dep, gdep, ft, gft = c(image), c(gt_image), c(depth), c(gt_depth), c(feat), c(gt_feat)
-        H, W = first.shape[-2], first.shape[-1]
-        for a, b, n, name in ((img, gt, 3 * H * W, "image"), (dep, gdep, H * W, "depth"), (ft, gft, 3 * H * W, "feat")):
-            if (a is None) != (b is None) or (a is not None and (a.numel() != n or b.numel() != n)):
-                raise RuntimeError(f"pixel_terms: {name} and its target must both be given, {n} elements each")
-        dev = first.device
-        sums = torch.zeros(5 * SUM_DOUBLES + 5, dtype=torch.float64, device=dev)
-        totals = sums[5 * SUM_DOUBLES:]
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        p = lambda t: None if t is None else t.data_ptr()
-        wl, wd, wf = (float(w_l1) if img is not None else 0.0, float(w_depth) if dep is not None else 0.0,
-                      float(w_feat) if ft is not None else 0.0)
-        with _lib.on_device(dev):
-            st = _lib.stream_ptr()
-            _lib.check(L.s3g_pixel_losses_forward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), float(max_depth), p(sums), st))
-            _lib.check(L.s3g_pixel_losses_combine(H, W, p(sums), p(totals), wl, wd, 0.0, wf, p(loss), st))
-        ctx.save_for_backward(*(t for t in (img, gt, dep, gdep, ft, gft) if t is not None), totals)
-        ctx.cfg = (H, W, img is not None, dep is not None, ft is not None, wl, wd, wf, float(max_depth),
-                   None if image is None else image.shape, None if depth is None else depth.shape, None if feat is None else feat.shape)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        H, W, has_i, has_d, has_f, wl, wd, wf, max_depth, ishape, dshape, fshape = ctx.cfg
-        saved = list(ctx.saved_tensors)
-        img = gt = dep = gdep = ft = gft = None
-        k = 0
-        if has_i:
-            img, gt = saved[k], saved[k + 1]
-            k += 2
-        if has_d:
-            dep, gdep = saved[k], saved[k + 1]
-            k += 2
-        if has_f:
-            ft, gft = saved[k], saved[k + 1]
-            k += 2
-        totals = saved[k]
-        L = _bind()
-        g = g.detach().reshape(1).contiguous().float()
-        need = ctx.needs_input_grad
-        g_img = _new_grad(img) if (has_i and need[0]) else None
-        g_dep = _new_grad(dep) if (has_d and need[2]) else None
-        g_ft = _new_grad(ft) if (has_f and need[4]) else None
-        p = lambda t: None if t is None else t.data_ptr()
-        with _lib.on_device(totals.device):
-            _lib.check(L.s3g_pixel_losses_backward(H, W, p(img), p(gt), p(dep), p(gdep), p(ft), p(gft), max_depth, p(totals), p(g),
-                                                   wl, wd, wf, p(g_img), 0, p(g_dep), p(g_ft), _lib.stream_ptr()))
-        return (None if g_img is None else g_img.view(ishape), None, None if g_dep is None else g_dep.view(dshape), None,
-                None if g_ft is None else g_ft.view(fshape), None, None, None, None, None)
+    return _photometric("photometric_loss_views", *lists, lambda_dssim, lambda_depth, lambda_feat, max_depth)
 
 
 def pixel_terms(image=None, gt_image=None, depth=None, gt_depth=None, feat=None, gt_feat=None, w_l1=0.0, w_depth=0.0,
                 w_feat=0.0, max_depth=80.0):
     """Any subset of: w_l1 * l1_loss(image, gt_image) [3,H,W]; w_depth * compute_depth("l2", depth, gt_depth) [1,H,W] or [H,W];
-    w_feat * l2_loss(feat, gt_feat) [3,H,W]   (utils/loss_utils.py:21-54)."""
+    w_feat * l2_loss(feat, gt_feat) [3,H,W]   (utils/loss_utils.py:21-54).  The zero-edit route (s3gaussian_amd.patch) calls it
+    once per term, because train.py:395-425 adds them one function call at a time; photometric_loss above is the all-in-one form.
+    H and W are the last two dims of the first tensor given; the others are checked by their element counts."""
     if image is None and depth is None and feat is None:
         raise RuntimeError("pixel_terms: nothing to do")
-    return _PixelTerms.apply(image, gt_image, depth, gt_depth, feat, gt_feat, w_l1, w_depth, w_feat, max_depth)
+    first = next(t for t in (image, depth, feat) if t is not None)
+    _require_gpu("pixel_terms", first)
+    H, W = first.shape[-2], first.shape[-1]
+    _require_pairs("pixel_terms", (("image", image, gt_image, 3 * H * W), ("depth", depth, gt_depth, H * W),
+                                   ("feat", feat, gt_feat, 3 * H * W)))
+    return _PixelLoss.apply(H, W, w_l1, 0.0, w_depth, w_feat, max_depth, image, gt_image, depth, gt_depth, feat, gt_feat)
 
 
-class _PlaneRegDesc(C.Structure):
-    """struct s3g_plane_reg_desc (include/s3g_loss.h)."""
-    _fields_ = [("plane", C.c_void_p), ("grad", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("w_smooth", C.c_float),
-                ("w_l1", C.c_float)]
+def _plane_regulation_launch(planes, weights, grads):
+    """Value of the regulariser over [1,32,H,W] channels_last `planes` with one (w_smooth, w_l1) per plane; the gradient of
+    plane i is written into grads[i] (include/s3g_loss.h::s3g_plane_regulation)."""
+    L = _bind()
+    dev = planes[0].device
+    if not planes[0].is_cuda:
+        raise RuntimeError("plane regulation: planes must live on the GPU; no CPU fallback")
+    descs = (_PlaneRegDesc * len(planes))()
+    for i, (p, g, (ws, wl)) in enumerate(zip(planes, grads, weights)):
+        if p.dim() != 4 or p.shape[1] != 32 or not p.is_contiguous(memory_format=torch.channels_last):
+            raise RuntimeError("plane regulation expects [1,32,H,W] channels_last planes")
+        if not g.is_contiguous(memory_format=torch.channels_last):
+            raise RuntimeError("plane regulation: gradient views must be channels_last")
+        descs[i] = _PlaneRegDesc(p.data_ptr(), g.data_ptr(), p.shape[2], p.shape[3], ws, wl)
+    value = torch.zeros(SUM_DOUBLES, dtype=torch.float64, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(L.s3g_plane_regulation(len(planes), descs, value.data_ptr(), _lib.stream_ptr()))
+    return value.sum().float()
 
 
 class _PlaneRegulation(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weights, *planes):
-        L = _lib.lib()
-        L.s3g_plane_regulation.restype = C.c_int
-        L.s3g_plane_regulation.argtypes = [C.c_int, C.POINTER(_PlaneRegDesc), C.c_void_p, C.c_void_p]
-        dev = planes[0].device
-        if not planes[0].is_cuda:
-            raise RuntimeError("plane regulation: planes must live on the GPU; no CPU fallback")
-        grads = [torch.empty_like(p) for p in planes]  # preserves channels_last
-        descs = (_PlaneRegDesc * len(planes))()
-        for i, (p, g, (ws, wl)) in enumerate(zip(planes, grads, weights)):
-            if p.dim() != 4 or p.shape[1] != 32 or not p.is_contiguous(memory_format=torch.channels_last):
-                raise RuntimeError("plane regulation expects [1,32,H,W] channels_last planes")
-            descs[i] = _PlaneRegDesc(p.data_ptr(), g.data_ptr(), p.shape[2], p.shape[3], ws, wl)
-        value = torch.zeros(SUM_DOUBLES, dtype=torch.float64, device=dev)
-        with _lib.on_device(dev):
-            _lib.check(L.s3g_plane_regulation(len(planes), descs, value.data_ptr(), _lib.stream_ptr()))
-        ctx.grads = grads
-        return value.sum().float()
+        ctx.grads = [torch.empty_like(p) for p in planes]  # preserves channels_last
+        return _plane_regulation_launch(planes, weights, ctx.grads)
 
     @staticmethod
     def backward(ctx, g):
@@ -403,31 +295,12 @@ def plane_regulation_into(planes, reg_weights, grad_views):
     """Value of compute_regulation over `planes` (level-major list of the 6 planes per level) with the gradient written
     into the caller's channels_last views (no autograd here: s3gaussian_amd.hexplane folds it into the sampler's node).
     reg_weights = (time_smoothness_weight, l1_time_planes_weight, plane_tv_weight)."""
-    L = _lib.lib()
-    L.s3g_plane_regulation.restype = C.c_int
-    L.s3g_plane_regulation.argtypes = [C.c_int, C.POINTER(_PlaneRegDesc), C.c_void_p, C.c_void_p]
-    dev = planes[0].device
-    weights = _plane_weights(len(planes), *reg_weights)
-    descs = (_PlaneRegDesc * len(planes))()
-    for i, (p, g, (ws, wl)) in enumerate(zip(planes, grad_views, weights)):
-        if p.dim() != 4 or p.shape[1] != 32 or not p.is_contiguous(memory_format=torch.channels_last):
-            raise RuntimeError("plane regulation expects [1,32,H,W] channels_last planes")
-        if not g.is_contiguous(memory_format=torch.channels_last):
-            raise RuntimeError("plane regulation: gradient views must be channels_last")
-        descs[i] = _PlaneRegDesc(p.data_ptr(), g.data_ptr(), p.shape[2], p.shape[3], ws, wl)
-    value = torch.zeros(SUM_DOUBLES, dtype=torch.float64, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(L.s3g_plane_regulation(len(planes), descs, value.data_ptr(), _lib.stream_ptr()))
-    return value.sum().float()
+    return _plane_regulation_launch(planes, _plane_weights(len(planes), *reg_weights), grad_views)
 
 
 def plane_regulation(grids, time_smoothness_weight, l1_time_planes_weight, plane_tv_weight):
-    """GaussianModel.compute_regulation (scene/gaussian_model.py:748-749) over HexPlaneField.grids, value and
-    gradient in one fused pass."""
-    planes, weights = [], []
-    for level in grids:
-        for i, p in enumerate(level):
-            planes.append(p)
-            weights.append((float(time_smoothness_weight), float(l1_time_planes_weight)) if i in (2, 4, 5)
-                           else (float(plane_tv_weight), 0.0))
+    """GaussianModel.compute_regulation (scene/gaussian_model.py:748-749) over HexPlaneField.grids (6 planes per level), value
+    and gradient in one fused pass."""
+    planes = [p for level in grids for p in level]
+    weights = _plane_weights(len(planes), time_smoothness_weight, l1_time_planes_weight, plane_tv_weight)
     return _PlaneRegulation.apply(tuple(weights), *planes)

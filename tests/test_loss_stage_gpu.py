@@ -1,5 +1,6 @@
-"""The strip-walking loss stage (csrc/ssim.hip): `ssim` and `photometric_loss` at shapes that straddle every edge of the
-tiling, on impulse images, fused against the separate entry points, and with poisoned output buffers.
+"""The strip-walking loss stage (csrc/ssim.hip; the separate per-pixel entry points and the combine: csrc/pixel_loss.hip): `ssim`
+and `photometric_loss` at shapes that straddle every edge of the tiling, on impulse images, fused against the separate entry
+points, and with poisoned output buffers.
 
 Reference: oracle.hexplane_ref evaluated in float64 on the CPU.  Bar per tensor (the rule of test_optim_trajectory_gpu.py):
     max |gpu - f64| <= 4 x max |the same restatement in float32 on the CPU - f64| + one float32 ulp of the tensor's largest magnitude

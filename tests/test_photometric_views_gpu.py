@@ -6,7 +6,10 @@ exact -- per view, which is no weaker than over the batch.
 
 H x W = 45 x 70 is ragged against the SSIM kernel's strips of 64 columns x 21 rows (two column strips, the second 6 wide; three
 row strips, the last 3 high).  The views have very different counts of valid depth pixels, one has none: the reference's depth
-term is the mean over the valid pixels of the whole batch, and a per-view reading is shown to be far outside the tolerance."""
+term is the mean over the valid pixels of the whole batch, and a per-view reading is shown to be far outside the tolerance.
+
+The public forms of the module share one node; the bit-for-bit tests below pin them against each other (a batch of one view is
+photometric_loss, pixel_terms with every pair is photometric_loss without SSIM, plane_regulation_into is plane_regulation)."""
 import pytest
 import torch
 
@@ -113,6 +116,66 @@ def test_joint_depth_normalisation_is_not_the_mean_of_per_view_means():
     assert W_DEPTH * abs(joint - mean_of_means) > 1000 * 5e-6 * max(1.0, abs(total)), (joint, mean_of_means)
     # gradient of view 0's depth: 1/(n0 + n1) under the joint count, 1/(2 n0) under the mean of two per-view means
     assert abs((counts[0] + counts[1]) / (2.0 * counts[0]) - 1.0) > 1000 * 1e-5
+
+
+def _value_and_grads(fn, leaves):
+    ls = [None if t is None else t.clone().requires_grad_(True) for t in leaves]
+    v = fn(*ls)
+    (2.5 * v).backward()
+    return v.detach(), [None if t is None else t.grad for t in ls]
+
+
+def _assert_same_bits(a, b):
+    (va, ga), (vb, gb) = a, b
+    assert torch.equal(va, vb), (va.item(), vb.item())
+    for k, (x, y) in enumerate(zip(ga, gb)):
+        assert (x is None) == (y is None), k
+        assert x is None or torch.equal(x, y), (k, (x - y).abs().max().item())
+
+
+@pytest.mark.parametrize("with_feat", [True, False], ids=["feat", "no_feat"])
+@pytest.mark.parametrize("w_ssim", [W_SSIM, 0.0], ids=["ssim", "no_ssim"])
+def test_one_view_batch_is_the_single_view_loss_bit_for_bit(gpu_device, w_ssim, with_feat):
+    """A batch of one view divides by 1 and by 1.0 where the single-view form does not divide: the same bits, value and gradients,
+    and None for the same gradients."""
+    from s3gaussian_amd.losses import photometric_loss, photometric_loss_views
+    img, gt, dep, gdep, ft, gft = (t[0].to(gpu_device) for t in _batch())
+    kw = dict(lambda_dssim=w_ssim, lambda_depth=W_DEPTH, lambda_feat=W_FEAT)
+    leaves = [img, dep, ft if with_feat else None]
+    tgt = lambda t: None if t is None else gft
+    single = _value_and_grads(lambda i, d, t: photometric_loss(i, gt, d, gdep, t, tgt(t), **kw), leaves)
+    batch = _value_and_grads(lambda i, d, t: photometric_loss_views([i], [gt], [d], [gdep], [t], [tgt(t)], **kw), leaves)
+    assert (single[1][2] is not None) == with_feat and single[1][0] is not None and single[1][1] is not None
+    _assert_same_bits(batch, single)
+
+
+def test_pixel_terms_with_all_pairs_is_the_loss_without_ssim_bit_for_bit(gpu_device):
+    from s3gaussian_amd.losses import photometric_loss, pixel_terms
+    img, gt, dep, gdep, ft, gft = (t[0].to(gpu_device) for t in _batch())
+    leaves = [img, dep, ft]
+    terms = _value_and_grads(lambda i, d, t: pixel_terms(i, gt, d, gdep, t, gft, w_l1=1.0, w_depth=W_DEPTH, w_feat=W_FEAT), leaves)
+    loss = _value_and_grads(lambda i, d, t: photometric_loss(i, gt, d, gdep, t, gft, lambda_dssim=0.0, lambda_depth=W_DEPTH,
+                                                             lambda_feat=W_FEAT), leaves)
+    assert all(g is not None for g in loss[1])
+    _assert_same_bits(terms, loss)
+
+
+def test_plane_regulation_into_writes_what_the_node_back_propagates(gpu_device):
+    """plane_regulation_into (the gradient lands in the caller's views) against plane_regulation + backward with an upstream
+    gradient of 1, on six planes of mixed sizes: one launch either way, the same value and gradients bit for bit."""
+    from s3gaussian_amd.losses import plane_regulation, plane_regulation_into
+    g = torch.Generator().manual_seed(6)
+    sizes = [(2, 3), (3, 5), (5, 2), (2, 2), (5, 5), (3, 2)]
+    planes = [torch.randn(1, 32, h, w, generator=g).to(gpu_device).contiguous(memory_format=torch.channels_last) for h, w in sizes]
+    weights = (0.01, 0.0001, 0.0002)
+    leaves = [p.clone().requires_grad_(True) for p in planes]
+    v = plane_regulation([leaves], *weights)
+    v.backward()
+    views = [torch.full_like(p, float("nan")) for p in planes]
+    vi = plane_regulation_into(planes, weights, views)
+    assert torch.isfinite(v).item() and torch.equal(vi, v.detach()), (vi.item(), v.item())
+    for k, (leaf, view) in enumerate(zip(leaves, views)):
+        assert torch.equal(leaf.grad, view), k
 
 
 def test_refusals(gpu_device):

@@ -2,7 +2,7 @@
 """Image-space loss stage: the tree's fused strip-walking launches against the parent commit's five kernels, in one process.
 
     python tools/loss_ab.py --build-parent [REV]     (CPU box: compiles REV's csrc/ssim.hip -- default HEAD -- with the Makefile's flags
-                                                      and links it with the tree's other objects into
+                                                      and links it with the tree's objects that define none of its entry points into
                                                       s3gaussian_amd/lib/variants/libs3g_loss_parent.so, as tools/mkvariants.py does)
     python tools/loss_ab.py [--reps 30] [--warmup 5] [--out profiles/loss_stage_ab_tool.txt]          (GPU box)
 
@@ -10,7 +10,7 @@ At 1066 x 1600 the tool loads the tree's library (the package's own) and the par
 seeded inputs of tests/test_loss_stage_gpu.py and on a rendered street-scene view with its targets:
 
   parent  s3g_ssim_forward + s3g_pixel_losses_forward + s3g_pixel_losses_combine; backward: the torch multiply g * (-w_ssim),
-          s3g_ssim_backward, s3g_pixel_losses_backward with accumulate_image = 1           (what losses._PhotometricLoss ran)
+          s3g_ssim_backward, s3g_pixel_losses_backward with accumulate_image = 1           (what losses.photometric_loss ran)
   tree    s3g_photometric_forward + s3g_pixel_losses_combine; backward: s3g_photometric_backward
 
 (a) Exactness.  The three maps, g_image, g_depth and g_feat of the two routes must be torch.equal.  The five totals are compared by
@@ -46,7 +46,12 @@ def build_parent(rev):
     finally:
         if os.path.exists(tmp_src):
             os.remove(tmp_src)
-    objs = [o for o in glob.glob(os.path.join(mk.LIB, "*.o")) if os.path.basename(o) != "ssim.o"] + [obj]
+    # REV's ssim.hip may hold more than the tree's (it held the pixel-loss and plane-regulariser families before they got files of
+    # their own): leave out every tree object that defines an entry point the parent object defines
+    exports = lambda o: {l.split()[-1] for l in subprocess.check_output(["nm", "--defined-only", o]).decode().splitlines()
+                         if l.split()[-1].startswith("s3g_")}
+    parent = exports(obj)
+    objs = [o for o in glob.glob(os.path.join(mk.LIB, "*.o")) if not exports(o) & parent] + [obj]
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", PARENT_SO])
     os.remove(obj)
     print(PARENT_SO)

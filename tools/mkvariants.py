@@ -19,7 +19,7 @@ SRC = os.path.join(ROOT, "s3gaussian_amd", "csrc")
 LIB = os.path.join(ROOT, "s3gaussian_amd", "lib")
 OUT = os.path.join(LIB, "variants")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics"]
-FILE_FLAGS = {"ssim.hip": ["-fno-slp-vectorize"]}      # the Makefile's per-file additions
+FILE_FLAGS = {hip: ["-fno-slp-vectorize"] for hip in ("ssim.hip", "pixel_loss.hip", "plane_reg.hip")}   # the Makefile's per-file additions
 
 
 def build(name, hip, edits):
