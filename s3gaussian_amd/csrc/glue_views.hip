@@ -2,13 +2,11 @@
 // and their gradients do not depend on the camera, only the view direction does.  One kernel each way reads f_dc / f_rest / dshs
 // once per Gaussian (421 B) and serves V cameras: V x 12 B of colours forward, V x 24 B backward, against V x ~440 B for V calls
 // of glue.hip.  Arithmetic per camera is glue.hip's, from the same source (glue_dev.hpp): colours are bit-identical to a
-// single-camera call, and with V = 1 so is every gradient.  The other per-Gaussian piece of a multi-view training step lives
-// here too: the densification statistics of a batch.
+// single-camera call, and with V = 1 so is every gradient.
 #include "glue_dev.hpp"
 
 #include "../../include/s3g_glue.h"
 #include "../../include/s3g_loss.h"  // S3G_SUM_* (slotted accumulators)
-#include "../../include/s3g_optim.h"
 
 namespace s3g {
 
@@ -203,36 +201,6 @@ __global__ void __launch_bounds__(R) glue_backward_views_kernel(const GlueViewsA
   }
 }
 
-// Densification statistics of a batch of views (train.py:387-388, 435-437, 489-493): the viewspace gradients are summed first
-// (left to right) and the norm is taken of the sum; a Gaussian counts once if any view saw it; the radius is the largest.
-struct StatsViewsArgs {
-  int P, V, stride;
-  const float* grad[S3G_DENSIFY_MAX_VIEWS];
-  const int* radii[S3G_DENSIFY_MAX_VIEWS];
-  float *accum, *denom, *max_radii;
-  const uint32_t* skip;
-};
-
-__global__ void __launch_bounds__(256) densify_stats_views_kernel(const StatsViewsArgs a) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.P) return;
-  if (a.skip && *a.skip != 0u) return;   // a forward of the batch overflowed: the batch's statistics do not exist (uniform load)
-  int r = a.radii[0][i];
-  bool vis = r > 0;
-  float gx = a.grad[0][(size_t)i * a.stride], gy = a.grad[0][(size_t)i * a.stride + 1];
-  for (int v = 1; v < a.V; v++) {
-    const int rv = a.radii[v][i];
-    vis = vis || rv > 0;
-    r = max(r, rv);
-    gx = gx + a.grad[v][(size_t)i * a.stride];
-    gy = gy + a.grad[v][(size_t)i * a.stride + 1];
-  }
-  if (!vis) return;
-  a.accum[i] += sqrtf(gx * gx + gy * gy);
-  a.denom[i] += 1.f;
-  a.max_radii[i] = fmaxf(a.max_radii[i], (float)r);
-}
-
 }  // namespace s3g
 
 using namespace s3g;
@@ -300,36 +268,4 @@ extern "C" int s3g_glue_backward_views(int P, int deg, int V, const float* f_dc,
   else hipLaunchKernelGGL(glue_backward_views_kernel<64>, dim3((P + 63) / 64), dim3(64), 0, st, a);
   S3G_HIP_CHECK(hipGetLastError());
   return S3G_OK;
-}
-
-static int densify_stats_views_impl(int P, int V, const float* const* grad_xy, int grad_stride, const int* const* radii,
-                                    float* xyz_gradient_accum, float* denom, float* max_radii2D, const uint32_t* skip, void* stream_) {
-  bool ok = P >= 0 && V >= 1 && V <= S3G_DENSIFY_MAX_VIEWS && grad_stride >= 2 && grad_xy != nullptr && radii != nullptr;
-  if (ok && P > 0) {
-    ok = xyz_gradient_accum && denom && max_radii2D;
-    for (int v = 0; ok && v < V; v++) ok = grad_xy[v] != nullptr && radii[v] != nullptr;
-  }
-  if (!ok) {
-    set_error("s3g_densify_stats_views: bad argument (1 <= V <= %d)", S3G_DENSIFY_MAX_VIEWS);
-    return S3G_ERR_INVALID_ARG;
-  }
-  if (P == 0) return S3G_OK;
-  StatsViewsArgs a;
-  memset(&a, 0, sizeof a);
-  a.P = P; a.V = V; a.stride = grad_stride;
-  for (int v = 0; v < V; v++) { a.grad[v] = grad_xy[v]; a.radii[v] = radii[v]; }
-  a.accum = xyz_gradient_accum; a.denom = denom; a.max_radii = max_radii2D; a.skip = skip;
-  hipLaunchKernelGGL(densify_stats_views_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream_, a);
-  S3G_HIP_CHECK(hipGetLastError());
-  return S3G_OK;
-}
-
-extern "C" int s3g_densify_stats_views(int P, int V, const float* const* grad_xy, int grad_stride, const int* const* radii,
-                                       float* xyz_gradient_accum, float* denom, float* max_radii2D, void* stream_) {
-  return densify_stats_views_impl(P, V, grad_xy, grad_stride, radii, xyz_gradient_accum, denom, max_radii2D, nullptr, stream_);
-}
-extern "C" int s3g_densify_stats_views_guarded(int P, int V, const float* const* grad_xy, int grad_stride, const int* const* radii,
-                                               float* xyz_gradient_accum, float* denom, float* max_radii2D,
-                                               const uint32_t* skip_flag, void* stream_) {
-  return densify_stats_views_impl(P, V, grad_xy, grad_stride, radii, xyz_gradient_accum, denom, max_radii2D, skip_flag, stream_);
 }

@@ -134,4 +134,53 @@ int launch_tile_sort(const Arenas& a, uint32_t* slot_map, uint32_t max_tile, con
 int launch_blend_forward(const Arenas& a, const float* colors, const float* bg, float* out_color, float* out_depth,
                          const float* colors2, float* out_color2, double instances, hipStream_t stream, bool debug);
 
+// ---- the stages of the backward, in the order raster_backward.hip issues them ------------------------------------------------
+// raster_blend_backward.hip: upstream image gradients -> records [R][NREC], or [R][NREC + 4] with two_images (colors2, dL_dpix2);
+// alpha: dL_dalpha [H*W] is the upstream gradient of the opacity image.  instances = R for the profile
+int launch_blend_backward(const Arenas& a, bool two_images, bool alpha, const float* colors, const float* bg,
+                          const float* dL_dpix, const float* dL_dpix_depth, float* records, const float* colors2,
+                          const float* dL_dpix2, const float* dL_dalpha, double instances, hipStream_t stream, bool debug);
+// raster_geom_backward.hip: records -> the per-Gaussian gradients.  The kernel's argument block, filled by raster_backward.hip:
+struct GeomBwdArgs {
+  int P, D, M;
+  const float* means3D;
+  const int* radii;
+  const float* shs;
+  const uint8_t* clamped;
+  const float* scales;
+  const float* rotations;
+  float scale_modifier;
+  const float* cov3Ds;  // precomputed or the forward's own
+  const float* view;
+  const float* proj;
+  const float* campos;
+  float fx, fy, tan_fovx, tan_fovy;
+  int W, H, gx;
+  // gather side
+  const ushort4* rect;
+  const uint32_t* gauss_off;
+  const uint32_t* slot_pos;
+  const uint32_t* tile_hi;        // absolute end of the written records of each tile
+  const float* records;           // [R][NREC]
+  const float4* conic_opacity;
+  const uint32_t* ctrl;           // forward's control words: ctrl[4] != 0 = asynchronous forward overflowed, nothing was binned
+  // outputs (every element of every output is written, zeros for culled Gaussians)
+  float* dL_dmean2D;        // [P,3]
+  float* dL_dconic;         // [P,4]  optional (may be NULL)
+  float* dL_dopacity;       // [P]
+  float* dL_dcolor;         // [P,3]
+  float* dL_dcolor2;        // [P,3]  second image's colours (two-image backward only)
+  float* dL_ddepth;         // [P]    optional (may be NULL)
+  float* dL_dmean3D;        // [P,3]
+  float* dL_dcov3D;         // [P,6]
+  float* dL_dsh;            // [P,M,3]
+  float* dL_dscale;         // [P,3]
+  float* dL_drot;           // [P,4]
+  // optional densification bookkeeping (train.py:489-493, scene/gaussian_model.py:693-695), all three or none
+  float* dens_accum;        // [P] xyz_gradient_accum += ||dL_dmean2D.xy|| where visible
+  float* dens_denom;        // [P] denom += 1 where visible
+  float* dens_max_radii;    // [P] max_radii2D = max(max_radii2D, radii) where visible
+};
+int launch_geometry_backward(const GeomBwdArgs& ga, bool two_images, hipStream_t stream, bool debug);
+
 }  // namespace s3g

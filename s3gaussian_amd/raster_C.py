@@ -239,13 +239,10 @@ def async_skip_flag(device=None):
     """int32 [1] device tensor (a view into the status ring): != 0 iff the most recent asynchronous forward on `device`
     overflowed its arena; None if there has been none.  optim.Adam.step() hands it to s3g_adam_step_guarded; a data-parallel
     run all-reduces it (MAX) first so that every replica drops the same step (dp.reduce_skip_flag)."""
-    if not _async_states:
-        return None
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    st = _async_states.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    st = _state_of(device)
     if st is None:
         return None
-    if st.flag_override is not None:     # the last training forward ran synchronously (memory fallback): its own word, see rasterize_gaussians
+    if st.flag_override is not None:    # the last training forward ran synchronously (memory fallback): its own word, see rasterize_gaussians
         return st.flag_override
     if st.last_slot is None:
         return None
@@ -266,10 +263,7 @@ def async_status(device=None, block=False) -> dict:
     """Counters of the asynchronous forwards on `device`: calls issued / drained, overflowed calls, mean true instance count of
     the drained calls, capacities per image size.  block=True waits for every outstanding status row first."""
     empty = {"enabled": ASYNC, "policy": POLICY, "calls": 0, "drained": 0, "overflows": [], "reissued": 0, "mean_instances": None, "capacity": {}}
-    if not _async_states:     # nothing issued yet (or a CPU-only process): do not touch the device runtime
-        return empty
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    st = _async_states.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    st = _state_of(device)
     if st is None:
         return empty
     st.drain(block=block)
@@ -280,7 +274,7 @@ def async_status(device=None, block=False) -> dict:
 
 
 def _state_of(device):
-    if not _async_states:
+    if not _async_states:     # nothing issued yet (or a CPU-only process): do not touch the device runtime
         return None
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     return _async_states.get(dev.index if dev.index is not None else torch.cuda.current_device())
@@ -318,10 +312,7 @@ def async_acknowledge(device=None) -> None:
 
 def async_reset_statistics(device=None) -> None:
     """Forget the drained-call counters (not the capacities): bench.py brackets its timed regions with this."""
-    if not _async_states:
-        return
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    st = _async_states.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    st = _state_of(device)
     if st is not None:
         st.drain(block=True)
         st.sum_instances, st.drained, st.overflows, st.frozen, st.reissued = 0, 0, [], [], 0

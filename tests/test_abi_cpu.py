@@ -258,3 +258,74 @@ def test_raster_arena_layout_is_what_the_single_file_library_carved():
         n = [C.c_size_t(), C.c_size_t(), C.c_size_t()]
         assert L.s3g_raster_arena_bytes(*case, C.byref(n[0]), C.byref(n[1]), C.byref(n[2])) == 0, case
         assert tuple(x.value for x in n) == want, (case, tuple(x.value for x in n))
+
+
+def test_raster_backward_workspace_sizes_are_the_recorded_literals():
+    """One record per instance: NREC = 10 floats (40 B), 14 for the two-image backward (56 B), the total rounded up to a multiple
+    of 128; a negative R counts as 0 and P does not enter.  The literals are what the single-file raster_backward.hip returned."""
+    from s3gaussian_amd import _lib
+    L = _lib.lib()
+    for P in (0, 1_000_003):
+        got = [L.s3g_raster_backward_workspace_bytes(P, R) for R in (-5, 0, 1, 3, 4, 1 << 24)]
+        assert got == [0, 0, 128, 128, 256, 671088640], (P, got)
+        got = [L.s3g_raster_backward2_workspace_bytes(P, R) for R in (-5, 0, 1, 2, 3, 1 << 24)]
+        assert got == [0, 0, 128, 128, 256, 939524096], (P, got)
+
+
+def test_raster_backward_exports_keep_their_host_side_contracts():
+    """The five backward exports check their arguments in one order before any device call (no GPU needed): an incomplete
+    s3g_densify_accum, then NULL inputs, then P == 0 -> S3G_OK, then NULL arrays; s3g_raster_backward_alpha first treats three NULL
+    accumulators as none and wants colors2 / dL_dpix2 / dL_dcolor2 together.  Every string is the one s3g_last_error gave for the
+    single-file raster_backward.hip, the export's own name in front."""
+    import ctypes as C
+    from s3gaussian_amd import _lib
+    L = _lib.lib()
+    OK, INVALID = 0, 1
+    # export -> index of the s3g_densify_accum argument (None: it takes none)
+    exports = {"s3g_raster_backward": None, "s3g_raster_backward_accum": -2, "s3g_raster_backward2": None,
+               "s3g_raster_backward2_accum": -2, "s3g_raster_backward_alpha": -2}
+    keep = []     # ctypes objects the calls point at
+
+    def call(name, inputs=None, dens=None, **at):
+        fn = getattr(L, name)
+        args = [0 if t is C.c_int else None for t in fn.argtypes]
+        if inputs is not None:
+            args[0] = C.byref(inputs)
+        if dens is not None:
+            args[exports[name]] = C.byref(dens)
+        for i, v in at.items():
+            args[int(i[1:])] = v
+        keep.append((inputs, dens))
+        rc = fn(*args)
+        return rc, L.s3g_last_error().decode()
+
+    def inputs_of(P):
+        s = _lib.RasterInputs()
+        s.P, s.width, s.height = P, 16, 16
+        return s
+
+    word = (C.c_float * 4)()
+    some = C.cast(word, C.c_void_p)
+    for name, dens_at in exports.items():
+        assert call(name) == (INVALID, f"{name}: NULL inputs")
+        assert call(name, inputs_of(0))[0] == OK
+        assert call(name, inputs_of(5)) == (INVALID, f"{name}: NULL array argument")
+        if dens_at is None:
+            continue
+        for missing in ("xyz_gradient_accum", "denom", "max_radii2D"):
+            d = _lib.DensifyAccum(some, some, some)
+            setattr(d, missing, None)
+            want = (INVALID, f"{name}: s3g_densify_accum needs all three arrays")
+            assert call(name, None, d) == want            # reported before the NULL inputs: the order of the checks
+            assert call(name, inputs_of(0), d) == want    # and before P == 0 returns
+        assert call(name, inputs_of(0), _lib.DensifyAccum(some, some, some))[0] == OK
+    # s3g_raster_backward_alpha(in, colors2 [1], R, radii, 3 arenas, workspace, dL_dpix, dL_dpix_depth, dL_dpix2 [10], dL_dalpha,
+    #                           dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dcolor2 [16], ...)
+    name = "s3g_raster_backward_alpha"
+    together = (INVALID, f"{name}: colors2, dL_dpix2 and dL_dcolor2 go together (all three or none)")
+    assert call(name, inputs_of(0), a1=some) == together                    # colors2 without dL_dpix2
+    assert call(name, None, a1=some, a10=some) == together                  # ... without dL_dcolor2; before the NULL inputs
+    assert call(name, inputs_of(0), a10=some, a16=some) == together
+    assert call(name, inputs_of(0), a1=some, a10=some, a16=some)[0] == OK
+    assert call(name, inputs_of(0), _lib.DensifyAccum(None, None, None))[0] == OK     # three NULL accumulators mean none
+    assert call(name, None, _lib.DensifyAccum(None, None, None)) == (INVALID, f"{name}: NULL inputs")

@@ -1,4 +1,4 @@
-"""optim.densify_stats_views (csrc/glue_views.hip::densify_stats_views_kernel): the densification statistics of a batch of V
+"""optim.densify_stats_views (csrc/densify_stats.hip::densify_stats_views_kernel): the densification statistics of a batch of V
 views that share one optimizer step (train.py:387-388, 435-437, 489-493) in one pass, against optim.densify_stats applied to
 what the reference forms first: the torch-summed viewspace gradient (`zeros + g0 + g1 ...`, left to right), any-visibility and
 the stacked-max radii.  Same additions in the same order, same sqrt: the accumulators are bit-equal."""

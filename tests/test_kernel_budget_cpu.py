@@ -64,14 +64,15 @@ def test_mlp_and_raster_kernels_do_not_spill(built):
     assert vgpr <= 256 and scratch == 0, (vgpr, scratch)
     vgpr, scratch = _one(mlp, "mlp_forward_presplit_kernel")
     assert vgpr <= 256 and scratch <= 16, (vgpr, scratch)          # three spilled dwords as built; more would show in its 0.55 ms
-    bwd = _resources("raster_backward.o")
+    bwd = {**_resources("raster_blend_backward.o"), **_resources("raster_geom_backward.o")}
+    assert len(bwd) == 6 and sum("blend_backward_kernel" in k for k in bwd) == 4 and sum("geometry_backward_kernel" in k for k in bwd) == 2, sorted(bwd)
     for k, (vgpr, scratch) in bwd.items():
         assert scratch == 0, (k, vgpr, scratch)
 
 
 def test_round4_latency_fixes_keep_their_occupancy(built):
     """The three late fixes of round 4 bought latency hiding with registers / LDS; each has a step it must stay under."""
-    bwd = _resources("raster_backward.o")
+    bwd = _resources("raster_geom_backward.o")
     for needle in ("geometry_backward_kernelILi0E", "geometry_backward_kernelILi3E"):
         vgpr, scratch = _one(bwd, needle)          # three tiles of a rect in flight: still five waves per SIMD (four tiles: 105)
         assert vgpr <= 96 and scratch == 0, (needle, vgpr, scratch)

@@ -1,4 +1,4 @@
-"""The lane algebra of raster_backward.hip::row_transpose_reduce, simulated: 13 (or 10) values per lane, 16 lanes per row,
+"""The lane algebra of raster_blend_backward.hip::row_transpose_reduce, simulated: 13 (or 10) values per lane, 16 lanes per row,
 29 masked DPP adds -> every lane of bank b ends with the row totals of values 4b .. 4b+3.
 
 DPP semantics used (gfx9): `v_add_f32_dpp dst, src, src  <perm> bank_mask:M` computes, for every lane whose bank (lane // 4 inside
