@@ -12,6 +12,8 @@
   render_flows()      <- the flow part of utils/video_utils.py:203-209, 252-299 (forward / backward scene-flow images, flow.py)
   evaluate_video()    <- utils/video_utils.py:116-349 + 439-499 in one pass: metrics, decomposition, flows and the uint8 strips the
                          reference hands to its video writer, from ONE render per camera (frames.py)
+  scene_from_lidar()  <- the LiDAR part of readWaymoInfo (scene/dataset_readers.py:752-779, 824-977): per-camera depth maps at any
+                         image size, the camera-frustum aabb and the voxel-sampled initial cloud (lidar.py)
 
 Adaptive density control -- GaussianParams.densify / prune / reset_opacity and the schedule of train.py:494-516 -- lives in
 density.py on kernels of its own (include/s3g_density.h).  Everything else outside that path (data readers, checkpoints'
@@ -869,6 +871,51 @@ def save_split_point_clouds(pc: GaussianParams, time: float, dynamic_pcd_path: s
                            "grid_pe / no_grid / static_mlp / empty_voxel; defor_depth 1, net_width 64, 128 grid features)")
     dx = net.deform_heads(xyz, _uniform_time(float(time), xyz.device), uniform_time=True, reg_weights=None, need_feat=False)[0]
     return split.export_split(pc, dx, dynamic_pcd_path, static_pcd_path)
+
+
+@torch.no_grad()
+def scene_from_lidar(sweeps, l2ws, c2ws, Ks, H: int, W: int, sh_degree: int = 3, hyper: Optional[SimpleNamespace] = None,
+                     device="cuda:0", x_range=(-2.0, 80.0), depth_range=(0.01, 80.0), point_offset: int = 3,
+                     voxel_size: float = 0.013, num_pts: Optional[int] = None, generator: Optional[torch.Generator] = None) -> Dict:
+    """The LiDAR part of the reference's set-up (readWaymoInfo, scene/dataset_readers.py:752-779, 824-977) at ANY image size.
+
+    sweeps: T fp32 [N_t,stride] tables (lidar.read_sweep gives the raw [N,10] rows; host tensors are uploaded once, as they are).
+    l2ws [T,4,4], c2ws [T*V,4,4], Ks [T*V,3,3]: float64 host arrays, the cameras timestamp-major as the reference lists them.
+    -> {"depth_maps": [T*V,H,W] fp32 (row t*V + v feeds the depth L2 term of camera v at timestamp t as gt_depth[None]),
+        "xyz": [M,3] fp32 and "colors": [M,3] float64, what GaussianParams.create_from_points takes,
+        "aabb": float64 [2,3] host array (min, max) of the camera frustums, what the deformation field's set_aabb(max, min) takes}
+    and, when `hyper` is given, "gaussians": GaussianParams(sh_degree, hyper) created from the three."""
+    import numpy as np
+    from . import lidar
+    dev = torch.device(device)
+    c2ws, Ks, l2ws = _np_f64(c2ws), _np_f64(Ks), _np_f64(l2ws)
+    T = len(sweeps)
+    if T < 1 or l2ws.shape[0] != T or c2ws.shape[0] % T != 0 or Ks.shape[0] != c2ws.shape[0]:
+        raise ValueError(f"scene_from_lidar: {T} sweeps, l2ws {l2ws.shape}, c2ws {c2ws.shape}, Ks {Ks.shape}: expected [T,4,4], [T*V,4,4], [T*V,3,3]")
+    V = c2ws.shape[0] // T
+    aabb = lidar.frustum_aabb(c2ws, Ks, H, W, depth_range)
+    tables = [s.to(dev) for s in sweeps]
+    cloud = lidar.LidarCloud(aabb, sum(int(s.shape[0]) for s in tables), dev)
+    maps = torch.empty((T * V, H, W), dtype=torch.float32, device=dev)
+    workspace = torch.empty(V * H * W, dtype=torch.int32, device=dev)
+    for t, rows in enumerate(tables):
+        w2c = np.stack([np.linalg.inv(c2ws[t * V + v]) for v in range(V)])
+        lidar.depth_maps(rows, l2ws[t], w2c, Ks[t * V:(t + 1) * V], H, W, x_range, point_offset, out=maps[t * V:(t + 1) * V],
+                         workspace=workspace)
+        cloud.add(rows, l2ws[t], x_range, point_offset)
+    xyz = cloud.finish(voxel_size, num_pts, generator)
+    colors = lidar.init_colors(xyz.shape[0], generator)
+    out = {"depth_maps": maps, "xyz": xyz, "colors": colors, "aabb": aabb}
+    if hyper is not None:
+        pc = GaussianParams(sh_degree, hyper).create_from_points(xyz, colors, dev)
+        pc._deformation.deformation_net.set_aabb(aabb[1].tolist(), aabb[0].tolist())
+        out["gaussians"] = pc
+    return out
+
+
+def _np_f64(a):
+    import numpy as np
+    return np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float64)
 
 
 VIDEO_KEYS = ("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs", "forward_flows", "backward_flows")
