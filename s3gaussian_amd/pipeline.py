@@ -920,13 +920,15 @@ def _np_f64(a):
 
 VIDEO_KEYS = ("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs", "forward_flows", "backward_flows")
 SKY_VIDEO_KEYS = ("opacities", "sky_masks", "gt_sky_masks")       # asked for through evaluate_video(sky_keys=...), not through keys=
+DEPTH_VIDEO_KEYS = ("depth_colors",)                              # asked for through evaluate_video(depth_keys=...)
 _VIDEO_SOURCE = {"rgbs": "render", "depths": "depth", "dynamic_rgbs": "render_d", "static_rgbs": "render_s", "opacities": "alpha"}
 _VIDEO_ONE_CHANNEL = ("depths", "opacities")
 
 
 def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: torch.Tensor, masks=None, num_cams: int = 3,
                    keys=("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs"), sink=None, host: bool = False,
-                   compute_metrics: bool = True, stage: str = "fine", lpips=None, sky_keys=(), sky_masks=None) -> Dict:
+                   compute_metrics: bool = True, stage: str = "fine", lpips=None, sky_keys=(), sky_masks=None, depth_keys=(),
+                   depth_bounds=(4.0, 120.0)) -> Dict:
     """The reference's evaluation loop with its videos' frames (utils/video_utils.py:116-349 render_func, then 439-499
     save_seperate_videos) from ONE render per camera: render(cam, return_decomposition=<a decomposition key is asked for>,
     extra_colors=<the frame's flow colours, if a flow key is asked for>) feeds metrics.image_metrics -- row i of the [N,5] table,
@@ -942,6 +944,12 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     reference's render_func never fills: the accumulated opacity of each render (render(return_alpha=True)); 1 - opacity, evaluated in
     fp32 from the opacity image and replicated to three channels (`1 - np.stack([frame] * 3, axis=-1)`); and the caller's
     `sky_masks` (one [H,W] / [1,H,W] tensor per camera, required by "gt_sky_masks"), replicated likewise.
+    depth_keys: any of DEPTH_VIDEO_KEYS, delivered like the other strips and behind the sky keys.  "depth_colors" is the reference's
+    depth_visualizer (utils/video_utils.py:27-33, the call save_seperate_videos carries commented out, :472-479): the render's depth
+    through the turbo map with the log curve, weighted by the render's accumulated opacity (render(return_alpha=True)), an
+    [H, num_cams * W, 3] strip written by depthvis.depth_colors beside the compose call -- not a compose job, not counted against
+    the 8.  depth_bounds = (lo, hi) as depth_colors takes them; a None entry is that frame's own opacity-weighted percentile bound,
+    found on the device.
     T = len(cameras) // num_cams timestamps; leftover cameras are rendered and counted in the metrics and appear in no strip.
     When a timestamp's last camera has been composed each of its strips goes to sink(key, timestamp_index, strip), in the order of
     `keys`; without a sink into result["frames"][key] (with one, those lists stay empty).  result["middle"][key] is the strip of
@@ -956,16 +964,23 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     compute_metrics=True).
     Flow keys run the loop through render_flows (its windowing of dx and colours; stage "fine", at least 2 * num_cams cameras); they
     and the decomposition keys need the fused deformation route, as render_flows does."""
+    from . import depthvis as _depthvis
     from . import frames as _frames
-    keys, sky_keys = tuple(keys), tuple(sky_keys)
+    keys, sky_keys, depth_keys = tuple(keys), tuple(sky_keys), tuple(depth_keys)
     unknown = [k for k in keys if k not in VIDEO_KEYS]
-    if unknown or not (keys or sky_keys) or len(set(keys)) != len(keys) or len(keys) > _frames.MAX_JOBS:
+    if unknown or not (keys or sky_keys or depth_keys) or len(set(keys)) != len(keys) or len(keys) > _frames.MAX_JOBS:
         raise RuntimeError(f"evaluate_video: keys must be distinct entries of {VIDEO_KEYS} (got {keys}); "
-                           f"{SKY_VIDEO_KEYS} are asked for through sky_keys=")
+                           f"{SKY_VIDEO_KEYS} are asked for through sky_keys=, {DEPTH_VIDEO_KEYS} through depth_keys=")
+    if any(k not in DEPTH_VIDEO_KEYS for k in depth_keys) or len(set(depth_keys)) != len(depth_keys):
+        raise RuntimeError(f"evaluate_video: depth_keys must be distinct entries of {DEPTH_VIDEO_KEYS} (got {depth_keys})")
+    depth_bounds = tuple(depth_bounds)
+    if len(depth_bounds) != 2 or any(b is not None and float(b) != float(b) for b in depth_bounds):
+        raise RuntimeError(f"evaluate_video: depth_bounds must be (lo, hi), each a number or None (got {depth_bounds})")
     if any(k not in SKY_VIDEO_KEYS for k in sky_keys) or len(set(sky_keys)) != len(sky_keys) or len(keys) + len(sky_keys) > _frames.MAX_JOBS:
         raise RuntimeError(f"evaluate_video: sky_keys must be distinct entries of {SKY_VIDEO_KEYS} (got {sky_keys}), and keys and "
                            f"sky_keys together at most {_frames.MAX_JOBS}")
-    keys = keys + sky_keys
+    compose_keys = keys + sky_keys                 # the jobs of frames.compose; the depth keys' strips follow them
+    keys = compose_keys + depth_keys
     n, N = int(num_cams), len(cameras)
     if n == 5:
         raise RuntimeError("evaluate_video: num_cams = 5 is refused: the reference rescales the two outer views of five with "
@@ -976,7 +991,7 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
         raise RuntimeError("evaluate_video: one ground-truth image (and one mask entry) per camera")
     if "gt_sky_masks" in keys and (sky_masks is None or len(sky_masks) != N):
         raise RuntimeError('evaluate_video: the sky key "gt_sky_masks" needs sky_masks=, one mask per camera')
-    want_alpha = any(k in ("opacities", "sky_masks") for k in keys)
+    want_alpha = any(k in ("opacities", "sky_masks") for k in keys) or bool(depth_keys)
     want_flow = any(k in ("forward_flows", "backward_flows") for k in keys)
     want_dec = any(k in ("dynamic_rgbs", "static_rgbs") for k in keys)
     if (want_flow or want_dec) and not (_fused_route(pc, pipe) and "fine" in stage):
@@ -991,7 +1006,7 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
         raise RuntimeError("evaluate_video: lpips needs compute_metrics=True")
     lpips_fn, lpips_table = _lpips_table(lpips, N, dev)
     result = {"frames": {k: [] for k in keys}, "middle": {}, "num_timestamps": T}
-    normalize = [k == "depths" for k in keys]
+    normalize = [k == "depths" for k in compose_keys]
     state = SimpleNamespace(strips=None, size=None, pending=None, ring={})
 
     def hand_over(t, strips):                  # device strips, or views of the pinned slots
@@ -1046,7 +1061,7 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
             raise RuntimeError(f"evaluate_video: camera {i} renders {H} x {W}, the first camera of its timestamp "
                                f"{state.size[0]} x {state.size[1]}: one strip holds images of one size")
         images = []
-        for k in keys:
+        for k in compose_keys:
             if k == "gt_rgbs":
                 images.append(gt)
             elif k == "forward_flows":
@@ -1064,7 +1079,10 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
                 if _VIDEO_SOURCE[k] not in pkg:
                     raise RuntimeError(f'evaluate_video: render() returned no "{_VIDEO_SOURCE[k]}" for key "{k}" on this route')
                 images.append(pkg[_VIDEO_SOURCE[k]])
-        _frames.compose(images, state.strips, c, normalize=normalize)
+        if compose_keys:
+            _frames.compose(images, state.strips[:len(compose_keys)], c, normalize=normalize)
+        for s in state.strips[len(compose_keys):]:          # "depth_colors"
+            _depthvis.depth_colors(pkg["depth"], pkg["alpha"], depth_bounds[0], depth_bounds[1], out=s, cam=c, num_cams=n)
         if c == n - 1:
             finish_timestamp(t)
             state.strips = None
