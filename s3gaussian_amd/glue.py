@@ -56,6 +56,7 @@ class _Glue(torch.autograd.Function):
                                           _lib.stream_ptr()))
         ctx.deg = int(deg)
         ctx.has_dshs = dshs is not None
+        ctx.campos_shape = campos.shape
         ctx.save_for_backward(f_dc, f_rest, dshs if dshs is not None else torch.empty(0, device=dev), xyz_c, campos_c, rr,
                               colors, scales, rot, opac)
         ctx.want_dshs_l1 = want_dshs_l1
@@ -84,7 +85,12 @@ class _Glue(torch.autograd.Function):
                                            _p(scales), _p(rot), _p(opac), _p(g_colors), _p(g_scales), _p(g_rot), _p(g_opac),
                                            _p(g_f_dc), _p(g_f_rest), _p(g_dshs), _p(g_xyz), _p(g_ls), _p(g_rr), _p(g_ol), _p(g_l1),
                                            _lib.stream_ptr()))
-        return None, g_f_dc, g_f_rest, g_dshs, g_xyz, None, g_ls, g_rr, g_ol, None
+        g_campos = None
+        if ctx.needs_input_grad[5]:
+            # the colours depend on xyz - campos only: dL/dcampos = -sum_p g_xyz[p], summed in double in a fixed order
+            from . import raster_C
+            g_campos = raster_C.camera_backward(P, dev, g_dir=g_xyz)[32:35].to(torch.float32).view(ctx.campos_shape)
+        return None, g_f_dc, g_f_rest, g_dshs, g_xyz, g_campos, g_ls, g_rr, g_ol, None
 
 
 def activations_and_colors(deg, f_dc, f_rest, dshs, xyz, campos, log_scales, rot_raw, opacity_logit, with_dshs_l1=False):
@@ -171,6 +177,10 @@ def activations_and_colors_views(deg, f_dc, f_rest, dshs, xyz, campos_list, log_
     (include/s3g_glue.h::s3g_glue_*_views): -> ([colors_0 .. colors_{V-1}], scales, rotations, opacity[, dshs_l1]).
     campos_list: V camera centres ([3] each) or one [V,3] tensor.  Colours are bit-identical to V single-camera calls; the
     gradients are their fp32 sum, view 0 first."""
+    if any(torch.is_tensor(cp) and cp.requires_grad for cp in ([campos_list] if torch.is_tensor(campos_list) else campos_list)) \
+            and torch.is_grad_enabled():
+        raise RuntimeError("activations_and_colors_views: a camera centre requires a gradient; camera gradients are served by "
+                           "activations_and_colors (one view per call) only")
     campos = campos_list if torch.is_tensor(campos_list) else torch.stack([torch.as_tensor(cp).reshape(3) for cp in campos_list])
     campos = campos.reshape(-1, 3)
     V = campos.shape[0]

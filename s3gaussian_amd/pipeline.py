@@ -518,7 +518,7 @@ def _view_result(image, means2D, radii, depth, image2, alpha, want_feat, return_
 
 def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torch.Tensor,
            scaling_modifier=1.0, override_color=None, stage="fine", return_decomposition=False, return_dx=False,
-           render_feat=False, densify_accum=None, extra_colors=None, return_alpha=False):
+           render_feat=False, densify_accum=None, extra_colors=None, return_alpha=False, pose=None, cam_index=None):
     """Mirror of gaussian_renderer/__init__.py::render.  `viewpoint_camera` is a dict with the fields the reference
     reads from a Camera (image_height/width, FoVx/FoVy or tanfovx/tanfovy, world_view_transform=viewmatrix,
     full_proj_transform=projmatrix, camera_center=campos, time).
@@ -530,7 +530,13 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
     (s3g_raster_forward_reuse); the images come back as out["extra"], a list of [3,H,W].  What the reference does with one more
     `render(..., override_color=c)` per image (utils/video_utils.py:267,284), on the fused route and the frame's own geometry.
     return_alpha (extension): out["alpha"] = the accumulated opacity [1,H,W] of the main render, 1 - the final transmittance of
-    each pixel (rasterizer.forward_alpha); differentiable, zeros for a model without Gaussians.  False launches nothing new."""
+    each pixel (rasterizer.forward_alpha); differentiable, zeros for a model without Gaussians.  False launches nothing new.
+    pose (extension): a pose.PoseRefiner; the camera is then rendered at its refined pose, pose.corrected(camera, cam_index), and
+    under autograd the loss back-propagates to the refiner's correction of that camera.  None launches nothing new."""
+    if pose is not None:
+        if cam_index is None:
+            raise RuntimeError("render(pose=...): cam_index says which of the refiner's cameras this is")
+        viewpoint_camera = pose.corrected(viewpoint_camera, cam_index)
     if extra_colors is not None and torch.is_grad_enabled():
         raise RuntimeError("render(extra_colors=...) is an inference extension: call it under torch.no_grad()")
     dev = pc.get_xyz.device
@@ -697,7 +703,7 @@ def psnr(img1, img2):
 
 
 def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: torch.Tensor, masks=None, stage="fine",
-             return_decomposition=False, lpips=None) -> Dict:
+             return_decomposition=False, lpips=None, pose=None) -> Dict:
     """The metric part of the reference's evaluation loop (utils/video_utils.py:169-241, 301-307): every camera is rendered under
     no_grad, frame i's {psnr, ssim, masked_psnr, masked_ssim, masked_pixels} goes into row i of one [N,5] device tensor
     (metrics.image_metrics), and that tensor is read back ONCE after the last frame.  masks: None, or one entry per camera (None
@@ -708,7 +714,9 @@ def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: 
     s3gaussian_amd.lpips_vgg.LPIPSVGG model (VGG16, what metrics.py reports), with the caller's weights: frame i's
     {total, tap0..tap4} goes into row i of an [N,6] device tensor that is read back with the metrics table; the result gains "lpips"
     (non_zero_mean of the totals, utils/video_utils.py:210, 305) and "lpips_per_frame" ([N,6] float64 on the host), the same keys
-    for either model.  Without a model nothing changes."""
+    for either model.  Without a model nothing changes.
+    pose: None, or a pose.PoseRefiner with one row per camera: camera i is rendered at pose.corrected(camera, i) (training views at
+    their refined poses; no gradient flows here)."""
     n = len(cameras)
     if len(gt_images) != n or (masks is not None and len(masks) != n):
         raise RuntimeError("evaluate: one ground-truth image (and one mask entry) per camera")
@@ -716,7 +724,8 @@ def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: 
     lpips_fn, lpips_table = _lpips_table(lpips, n, pc.get_xyz.device)
     with torch.no_grad():
         for i, cam in enumerate(cameras):
-            pkg = render(cam, pc, pipe, bg, stage=stage, return_decomposition=return_decomposition)
+            pkg = render(cam, pc, pipe, bg, stage=stage, return_decomposition=return_decomposition,
+                         **({"pose": pose, "cam_index": i} if pose is not None else {}))
             _metrics.image_metrics(pkg["render"], gt_images[i], None if masks is None else masks[i], out=table[i])
             if lpips is not None:
                 lpips_fn(lpips, pkg["render"], gt_images[i], out=lpips_table[i])
@@ -928,7 +937,7 @@ _VIDEO_ONE_CHANNEL = ("depths", "opacities")
 def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: torch.Tensor, masks=None, num_cams: int = 3,
                    keys=("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs"), sink=None, host: bool = False,
                    compute_metrics: bool = True, stage: str = "fine", lpips=None, sky_keys=(), sky_masks=None, depth_keys=(),
-                   depth_bounds=(4.0, 120.0)) -> Dict:
+                   depth_bounds=(4.0, 120.0), pose=None) -> Dict:
     """The reference's evaluation loop with its videos' frames (utils/video_utils.py:116-349 render_func, then 439-499
     save_seperate_videos) from ONE render per camera: render(cam, return_decomposition=<a decomposition key is asked for>,
     extra_colors=<the frame's flow colours, if a flow key is asked for>) feeds metrics.image_metrics -- row i of the [N,5] table,
@@ -981,6 +990,9 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
                            f"sky_keys together at most {_frames.MAX_JOBS}")
     compose_keys = keys + sky_keys                 # the jobs of frames.compose; the depth keys' strips follow them
     keys = compose_keys + depth_keys
+    if pose is not None:    # a pose.PoseRefiner with one row per camera: every frame at its refined pose (no gradient flows here)
+        with torch.no_grad():
+            cameras = [pose.corrected(cam, i) for i, cam in enumerate(cameras)]
     n, N = int(num_cams), len(cameras)
     if n == 5:
         raise RuntimeError("evaluate_video: num_cams = 5 is refused: the reference rescales the two outer views of five with "
@@ -1239,7 +1251,8 @@ def _finish_step(pc: GaussianParams, pkgs, grad_hook, optimizer_step) -> None:
 
 
 def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hyper, opt, bg, stage="fine",
-                  pipe: Optional[SimpleNamespace] = None, grad_hook=None, densify_stats=False, optimizer_step=None, sky_mask=None):
+                  pipe: Optional[SimpleNamespace] = None, grad_hook=None, densify_stats=False, optimizer_step=None, sky_mask=None,
+                  pose=None, cam_index=None):
     """One iteration of train.py for one view: render -> loss -> backward -> Adam step.  `grad_hook(pc, pkg)` runs
     between backward and the optimizer step (used by the data-parallel wrapper for the RCCL all-reduce).
     densify_stats=True also does the bookkeeping of train.py:489-493 (max_radii2D, xyz_gradient_accum, denom) for this
@@ -1250,12 +1263,19 @@ def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hy
     dp.OverlappedGradAllReducer.finish_and_step, which steps the early-reduced groups while the last collectives are in flight).
     sky_mask with opt.lambda_sky != 0 (extension): the render also returns its opacity image and the loss gains
     lambda_sky * sky.sky_opacity_loss; its gradient rides in the same rasterizer backward, fused densify statistics included.
-    Without a mask, or with lambda_sky = 0, nothing new is launched."""
+    Without a mask, or with lambda_sky = 0, nothing new is launched.
+    pose (extension): a pose.PoseRefiner with cam_index = this camera's row in it: the view is rendered at its refined pose and
+    the refiner's optimizer steps and clears beside the model's.  Not under the data-parallel wrapper.  None: nothing new."""
     pipe = _default_pipe(pipe)
+    if pose is not None:
+        from . import dp as _dp
+        if _dp.active():
+            raise RuntimeError("training_step(pose=...): pose refinement under the data-parallel wrapper (dp) is not served")
     acc = (pc.xyz_gradient_accum, pc.denom, pc.max_radii2D) if densify_stats else None
     want_sky = _sky_weight(opt, sky_mask) != 0.0
     pkg = render(cam, pc, pipe, bg, stage=stage, return_dx=True, render_feat=(stage == "fine" and hyper.feat_head),
-                 densify_accum=acc, **({"return_alpha": True} if want_sky else {}))
+                 densify_accum=acc, **({"return_alpha": True} if want_sky else {}),
+                 **({"pose": pose, "cam_index": cam_index} if pose is not None else {}))
     loss = training_loss(pc, pkg, gt_image, gt_depth, gt_feat, hyper, opt, stage, **({"sky_mask": sky_mask} if want_sky else {}))
     loss.backward()
     if densify_stats and not pkg.get("densify_stats_fused", False):
@@ -1265,6 +1285,8 @@ def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hy
             vg = torch.zeros_like(pkg["viewspace_points"])
         _densify_stats(pc.xyz_gradient_accum, pc.denom, pc.max_radii2D, vg, pkg["radii"])
     _finish_step(pc, pkg, grad_hook, optimizer_step)
+    if pose is not None:
+        pose.step()
     return loss.detach(), pkg
 
 
@@ -1291,6 +1313,10 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
     from . import raster_C
     from .glue import MAX_VIEWS, activations_and_colors_views
     V = len(cams)
+    if torch.is_grad_enabled() and any(torch.is_tensor(cam.get(k)) and cam[k].requires_grad
+                                       for cam in cams for k in ("viewmatrix", "projmatrix", "campos")):
+        raise RuntimeError("render_views: a camera requires a gradient; camera gradients (pose refinement) are served by render() "
+                           "/ training_step(), one view per call, only")
     flags = [bool(render_feat)] * V if isinstance(render_feat, (bool, int)) else [bool(f) for f in render_feat]
     if len(flags) != V:
         raise RuntimeError(f"render_views: render_feat has {len(flags)} entries for {V} views")

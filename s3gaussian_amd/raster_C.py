@@ -670,17 +670,19 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
 
 def rasterize_gaussians_backward2(background, means3D, radii, colors, colors2, scales, rotations, scale_modifier,
                                   cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
-                                  dL_dout_color2, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, densify_accum=None):
+                                  dL_dout_color2, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, densify_accum=None,
+                                  return_internals=False):
     """Backward of two renders of the same geometry (colours `colors` -> image + depth, `colors2` -> second image) in one
     pass (include/s3g_raster.h::s3g_raster_backward2).
     -> (dL_dmeans2D, dL_dcolors, dL_dcolors2, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dscales, dL_drotations); everything
     but the two colour gradients is the sum over both images.
     densify_accum = (xyz_gradient_accum [P,1], denom [P,1], max_radii2D [P]) float32: the per-Gaussian kernel also does the
-    reference's add_densification_stats / max_radii2D update (s3g_raster_backward2_accum)."""
+    reference's add_densification_stats / max_radii2D update (s3g_raster_backward2_accum).
+    return_internals=True appends (dL_dconic[P,2,2], dL_ddepths[P,1]) like rasterize_gaussians_backward."""
     grads = _backward(background, means3D, radii, colors, colors2, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                       projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_color2, None, None, 0, campos, geomBuffer,
-                      R, binningBuffer, imageBuffer, debug, densify_accum, False)
-    return _ordered(grads, ("means2D", "colors", "colors2", "opacity", "means3D", "cov3D", "scales", "rot"))
+                      R, binningBuffer, imageBuffer, debug, densify_accum, return_internals)
+    return _ordered(grads, ("means2D", "colors", "colors2", "opacity", "means3D", "cov3D", "scales", "rot"), return_internals)
 
 
 def raster_alpha(imageBuffer, image_height, image_width):
@@ -711,6 +713,43 @@ def rasterize_gaussians_backward_alpha(background, means3D, radii, colors, color
                       projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_color2, dL_dout_alpha, sh, degree, campos,
                       geomBuffer, R, binningBuffer, imageBuffer, debug, densify_accum, return_internals)
     return _ordered(grads, ("means2D", "colors", "colors2", "opacity", "means3D", "cov3D", "sh", "scales", "rot"), return_internals)
+
+
+def camera_backward(P, device, *, means3D=None, radii=None, geomBuffer=None, viewmatrix=None, projmatrix=None, campos=None,
+                    tan_fovx=0.0, tan_fovy=0.0, image_height=0, image_width=0, dL_dmeans2D=None, dL_dconic=None,
+                    dL_ddepths=None, dL_dcolors=None, sh=None, degree=0, cov3D_precomp=None, g_dir=None, debug=False):
+    """Extension: the camera gradients of one rasterizer backward (include/s3g_camera.h::s3g_camera_backward), from that backward's
+    per-Gaussian outputs (`rasterize_gaussians_backward(..., return_internals=True)`) and the arenas of its forward.
+    -> float64 [35] on `device`: dL/dviewmatrix [16], dL/dprojmatrix [16], dL/dcampos [3], row-major like the matrices.
+    Every gradient array is optional (None drops its terms); g_dir [P,3] is the gradient, with respect to the mean, of colours that
+    were precomputed from mean - campos outside the rasterizer.  With g_dir alone only P and the device are needed."""
+    L = _lib.lib()
+    P = int(P)
+    out = torch.empty(35, dtype=torch.float64, device=device)
+    f32 = lambda t, name: None if (t is None or t.numel() == 0) else _f32(t, name)
+    keep = [f32(means3D, "means3D"), f32(sh, "sh"), f32(cov3D_precomp, "cov3D_precomp"), f32(viewmatrix, "viewmatrix"),
+            f32(projmatrix, "projmatrix"), f32(campos, "campos"), f32(dL_dmeans2D, "dL_dmeans2D"), f32(dL_dconic, "dL_dconic"),
+            f32(dL_ddepths, "dL_ddepths"), f32(dL_dcolors, "dL_dcolors"), f32(g_dir, "g_dir"),
+            None if radii is None else radii.contiguous()]
+    m3_, sh_, cov_, view_, proj_, cam_, g2d_, gcon_, gdep_, gcol_, gdir_, radii_ = keep
+    for name, t, width in (("means3D", m3_, 3), ("dL_dmeans2D", g2d_, 3), ("dL_dconic", gcon_, 4), ("dL_ddepths", gdep_, 1),
+                           ("dL_dcolors", gcol_, 3), ("g_dir", gdir_, 3), ("cov3D_precomp", cov_, 6)):
+        if t is not None and t.numel() != width * P:
+            raise RuntimeError(f"camera_backward: {name} must have {P} x {width} elements, got {tuple(t.shape)}")
+    if radii_ is not None and (radii_.numel() != P or radii_.dtype != torch.int32):
+        raise RuntimeError(f"camera_backward: radii must be int32 [{P}]")
+    M = sh_.size(1) if sh_ is not None else 0
+    if sh_ is not None and sh_.numel() != P * M * 3:
+        raise RuntimeError(f"camera_backward: sh must be [{P}, M, 3]")
+    inp = _inputs(P, degree, M, image_width, image_height, None, m3_, sh_, None, None, None, 1.0, None, cov_, view_, proj_,
+                  tan_fovx, tan_fovy, cam_, False, debug)
+    work = torch.empty(L.s3g_camera_backward_workspace_bytes(P), dtype=torch.uint8, device=device)
+    ptr = lambda t: _ptr(t) or None
+    with _lib.on_device(out.device):
+        code = L.s3g_camera_backward(C.byref(inp), ptr(radii_), ptr(geomBuffer), ptr(g2d_), ptr(gcon_), ptr(gdep_), ptr(gcol_),
+                                     ptr(gdir_), ptr(work), out.data_ptr(), _lib.stream_ptr())
+    _lib.check(code)
+    return out
 
 
 def _densify_struct(acc, P) -> _lib.DensifyAccum:

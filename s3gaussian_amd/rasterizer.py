@@ -38,6 +38,32 @@ def _or_zero_images(grads, channels, rs, device):
     return [torch.zeros((c, rs.image_height, rs.image_width), device=device) if g is None else g for g, c in zip(grads, channels)]
 
 
+def _camera_inputs(rs) -> tuple:
+    """(viewmatrix, projmatrix, campos) of the settings when autograd wants a gradient for one of them, else ().  The settings are
+    a NamedTuple and no autograd input: the nodes below take the three tensors as real inputs behind their other arguments, ask
+    their backward for the internals and hand them to raster_C.camera_backward.  Without a camera that requires a gradient
+    nothing changes: the same call, the same launches, the same ctx."""
+    cams = (rs.viewmatrix, rs.projmatrix, rs.campos)
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cams):
+        return cams
+    return ()
+
+
+def _camera_grads(ctx, first, means3D, radii, geom, sh, cov3Ds_precomp, g_means2D, g_conic, g_depths, g_colors) -> tuple:
+    """The gradients of the three camera inputs (positions first .. first + 2 of the node), fp32 in the tensors' shapes."""
+    rs = ctx.raster_settings
+    has_sh = sh is not None and sh.numel() != 0
+    g = _C.camera_backward(means3D.size(0), means3D.device, means3D=means3D, radii=radii, geomBuffer=geom, viewmatrix=rs.viewmatrix,
+                           projmatrix=rs.projmatrix, campos=rs.campos, tan_fovx=rs.tanfovx, tan_fovy=rs.tanfovy,
+                           image_height=rs.image_height, image_width=rs.image_width, dL_dmeans2D=g_means2D, dL_dconic=g_conic,
+                           dL_ddepths=g_depths, dL_dcolors=g_colors if has_sh else None, sh=sh if has_sh else None,
+                           degree=rs.sh_degree, cov3D_precomp=cov3Ds_precomp, debug=rs.debug)
+    g32 = g.to(torch.float32)
+    parts = (g32[:16], g32[16:32], g32[32:35])
+    return tuple(part.view(t.shape) if need else None
+                 for part, t, need in zip(parts, (rs.viewmatrix, rs.projmatrix, rs.campos), ctx.needs_input_grad[first:first + 3]))
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """autograd node; forward keeps the three private arenas alive for backward (reference :44-156).
     with_alpha (extension): the accumulated opacity A = 1 - final_T as a fourth, differentiable output: one image-sized pass forward
@@ -46,8 +72,10 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                forward_only=False, with_alpha=False):
+                forward_only=False, with_alpha=False, viewmatrix=None, projmatrix=None, campos=None):
         rs = raster_settings
+        if viewmatrix is not None:
+            ctx.camera = True       # (viewmatrix, projmatrix, campos) = the settings' own tensors: _camera_inputs
         native_args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                        rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
                        rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
@@ -77,6 +105,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
         grad_out_color, grad_out_depth = _or_zero_images((grad_out_color, grad_out_depth), (3, 1), rs, means3D.device)
+        camera = getattr(ctx, "camera", False)
+        internals = dict(return_internals=True) if camera else {}
         if grad_alpha is None:
             native_args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_out_depth, sh,
@@ -84,21 +114,22 @@ class _RasterizeGaussians(torch.autograd.Function):
             if rs.debug:
                 saved = _snapshot(native_args)
                 try:
-                    grads = _C.rasterize_gaussians_backward(*native_args)
+                    grads = _C.rasterize_gaussians_backward(*native_args, **internals)
                 except Exception:
                     torch.save(saved, "snapshot_bw.dump")
                     print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                     raise
             else:
-                grads = _C.rasterize_gaussians_backward(*native_args)
-            g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rot = grads
+                grads = _C.rasterize_gaussians_backward(*native_args, **internals)
+            g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rot, *g_int = grads
         else:
-            (g_means2D, g_colors, _, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rot) = _C.rasterize_gaussians_backward_alpha(
+            (g_means2D, g_colors, _, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rot, *g_int) = _C.rasterize_gaussians_backward_alpha(
                 rs.bg, means3D, radii, colors_precomp, None, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_out_depth, None, grad_alpha, sh, rs.sh_degree, rs.campos,
-                geom, ctx.num_rendered, binning, img, rs.debug)
+                geom, ctx.num_rendered, binning, img, rs.debug, **internals)
         # order of forward's inputs: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, ...
-        return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rot, g_cov3D, None, None, None
+        g_camera = _camera_grads(ctx, 11, means3D, radii, geom, sh, cov3Ds_precomp, g_means2D, *g_int, g_colors) if camera else ()
+        return (g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rot, g_cov3D, None, None, None, *g_camera)
 
 
 class _RasterizeGaussiansPair(torch.autograd.Function):
@@ -108,8 +139,10 @@ class _RasterizeGaussiansPair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, colors_a, colors_b, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                densify_accum=None, forward_only=False, with_alpha=False):
+                densify_accum=None, forward_only=False, with_alpha=False, viewmatrix=None, projmatrix=None, campos=None):
         rs = raster_settings
+        if viewmatrix is not None:
+            ctx.camera = True       # see _RasterizeGaussians
         empty = torch.Tensor([])
         common = (opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
                   rs.tanfovy, rs.image_height, rs.image_width, empty, rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
@@ -133,13 +166,17 @@ class _RasterizeGaussiansPair(torch.autograd.Function):
         head = (rs.bg, means3D, radii, colors_a, colors_b, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_color2)
         tail = (rs.campos, geom, ctx.num_rendered, binning, img, rs.debug)
+        camera = getattr(ctx, "camera", False)
+        internals = dict(return_internals=True) if camera else {}
         if grad_alpha is None:
-            (g_means2D, g_col_a, g_col_b, g_opac, g_means3D, g_cov3D, g_scales, g_rot) = _C.rasterize_gaussians_backward2(
-                *head, *tail, densify_accum=ctx.densify_accum)
+            (g_means2D, g_col_a, g_col_b, g_opac, g_means3D, g_cov3D, g_scales, g_rot, *g_int) = _C.rasterize_gaussians_backward2(
+                *head, *tail, densify_accum=ctx.densify_accum, **internals)
         else:
-            (g_means2D, g_col_a, g_col_b, g_opac, g_means3D, g_cov3D, _, g_scales, g_rot) = _C.rasterize_gaussians_backward_alpha(
-                *head, grad_alpha, torch.Tensor([]), 0, *tail, densify_accum=ctx.densify_accum)
-        return g_means3D, g_means2D, g_col_a, g_col_b, g_opac, g_scales, g_rot, g_cov3D, None, None, None, None
+            (g_means2D, g_col_a, g_col_b, g_opac, g_means3D, g_cov3D, _, g_scales, g_rot, *g_int) = _C.rasterize_gaussians_backward_alpha(
+                *head, grad_alpha, torch.Tensor([]), 0, *tail, densify_accum=ctx.densify_accum, **internals)
+        # both colour sets are precomputed: the camera centre enters neither image
+        g_camera = _camera_grads(ctx, 12, means3D, radii, geom, None, cov3Ds_precomp, g_means2D, *g_int, None) if camera else ()
+        return (g_means3D, g_means2D, g_col_a, g_col_b, g_opac, g_scales, g_rot, g_cov3D, None, None, None, None, *g_camera)
 
 
 def _check_arguments(scales, rotations, cov3D_precomp, colour_sources=None):
@@ -165,6 +202,9 @@ def _no_backward(*tensors) -> bool:
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
     tensors = (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+    cams = _camera_inputs(raster_settings)
+    if cams:
+        return _RasterizeGaussians.apply(*tensors, raster_settings, False, False, *cams)
     return _RasterizeGaussians.apply(*tensors, raster_settings, _no_backward(*tensors))
 
 
@@ -193,7 +233,8 @@ class GaussianRasterizer(nn.Module):
         _check_arguments(scales, rotations, cov3D_precomp, colour_sources=(shs, colors_precomp))
         tensors = (means3D, means2D, _or_empty(shs), _or_empty(colors_precomp), opacities, _or_empty(scales), _or_empty(rotations),
                    _or_empty(cov3D_precomp))
-        return _RasterizeGaussians.apply(*tensors, self.raster_settings, _no_backward(*tensors), True)
+        cams = _camera_inputs(self.raster_settings)
+        return _RasterizeGaussians.apply(*tensors, self.raster_settings, False if cams else _no_backward(*tensors), True, *cams)
 
     @torch.no_grad()
     def forward_decomposed(self, means3D, opacities, dynamic_mask, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -240,4 +281,6 @@ class GaussianRasterizer(nn.Module):
                                    cov3D_precomp=cov3D_precomp)
             return (a, radii, depth, b, *alpha)
         tensors = (means3D, means2D, colors_a, colors_b, opacities, _or_empty(scales), _or_empty(rotations), _or_empty(cov3D_precomp))
-        return _RasterizeGaussiansPair.apply(*tensors, self.raster_settings, densify_accum, _no_backward(*tensors), bool(with_alpha))
+        cams = _camera_inputs(self.raster_settings)
+        return _RasterizeGaussiansPair.apply(*tensors, self.raster_settings, densify_accum, False if cams else _no_backward(*tensors),
+                                             bool(with_alpha), *cams)
