@@ -111,8 +111,9 @@ int s3g_raster_forward2(const s3g_raster_inputs* in, const float* colors2,
  * instances and rect slots as it is prepared to hold, e.g. twice the largest count it has seen -- and the call only enqueues
  * kernels: the host can run any number of iterations ahead of the GPU.
  *   arenas            device, at least s3g_raster_arena_bytes(...) bytes each, 128-byte aligned, caller-owned;
- *   sort_lds_keys     estimate of the longest per-tile list (sizes the LDS buffer of the short-list sort launch; lists that
- *                     exceed it are sorted in global memory; 0 = 4096);
+ *   sort_lds_keys     estimate of the longest per-tile list, 0 = 4096.  It sizes the LDS buffers of the sort launches for lists of
+ *                     at most 4096 instances and decides nothing else: a list that exceeds it is sorted all the same, in
+ *                     global memory (slower, same result), so a wrong estimate costs time and never correctness;
  *   long_lists        != 0: also launch the long-list sort pass (lists of more than 4096 instances);
  *   status_device     optional device word, written by EVERY call: bit 0 = the counts exceeded the capacity (instances >
  *                     capacity_instances, slots > capacity_slots, or a list > 4096 with long_lists == 0), bit 1 = a Gaussian was
@@ -240,6 +241,29 @@ int s3g_raster_set_backward_wave_bounds(int on);
  * bands of consecutive tiles, one pair of launches per band; results are identical.  Testing hook: force a smaller band
  * (returns the previous size; tiles <= 0 restores the default) so the band path can be exercised on small images. */
 int s3g_raster_set_bin_band(int tiles);
+
+/* Testing hook: the launches of the per-tile sort as the forward would issue them -- a pure host function, no device is touched.
+ * A launch runs one workgroup of `threads` threads per tile with `lds_bytes` of dynamic LDS; tiles whose list length n has
+ * lo < n <= hi sort it: in LDS when n <= lds_keys (bucket pass when bucket_keys != 0 and 512 < n <= bucket_keys), else in global
+ * memory.  asynchronous == 0: the plan of s3g_raster_forward for a longest list of `keys` (long_lists ignored); != 0: the plan of
+ * s3g_raster_forward_async for sort_lds_keys = `keys` and `long_lists`.  count_cap_tile is the list length above which the
+ * counting kernel of that forward declares an overflow (0: the synchronous forward has no such check; 0xffffffff: none can
+ * exceed it): the launches must cover every length up to it exactly once whatever `keys` says.  The last five words are the
+ * constants the plan was made with.  tests/test_sort_plan_cpu.py walks the plan length by length. */
+typedef struct s3g_sort_launch {
+  uint32_t threads, lds_bytes, lo, hi, lds_keys, bucket_keys;
+} s3g_sort_launch;
+typedef struct s3g_sort_plan {
+  uint32_t launches;            /* 1 .. 3 */
+  s3g_sort_launch launch[3];
+  uint32_t count_cap_tile;
+  uint32_t max_lds_bytes;       /* the dynamic LDS the library allows the sort kernel (hipFuncAttributeMaxDynamicSharedMemorySize) */
+  uint32_t bucket_min;          /* 512: longer lists take the bucket pass where a launch has room for it */
+  uint32_t small_keys;          /* 4096 */
+  uint32_t bucket_lds_extra;    /* bytes behind the two key buffers of the bucket pass */
+  uint32_t rank_direct;         /* lists of at most this many keys are ranked by counting, one thread per key */
+} s3g_sort_plan;
+int s3g_raster_sort_plan(int asynchronous, uint32_t keys, int long_lists, s3g_sort_plan* plan);
 
 /* present[P] (uint8 0/1) = in_frustum (auxiliary.h:139-164: view-space z > 0.2). */
 int s3g_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

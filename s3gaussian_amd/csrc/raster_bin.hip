@@ -345,7 +345,7 @@ int launch_bin_scan(int P, const Arenas& a, const s3g_raster_async* as, hipStrea
   S3G_KERNEL_CHECK(stream, debug);
   hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(1024), 0, stream, tiles, im.tile_count, im.ranges, im.ctrl, nb,
                      im.chunk_total, as ? as->capacity_instances : 0u, as ? as->capacity_slots : 0u,
-                     as ? (as->long_lists ? 0xffffffffu : SORT_SMALL_KEYS) : 0u, as ? as->status_device : nullptr,
+                     sort_list_cap(as), as ? as->status_device : nullptr,
                      (as && !as->forward_only) ? as->sticky_device : nullptr);
   S3G_KERNEL_CHECK(stream, debug);
   return S3G_OK;

@@ -12,6 +12,11 @@ constexpr int MAX_TILES_LDS = 38000;  // (160 KiB - slack) / 4 B: largest tile g
 constexpr int NREC = 10;              // floats per instance gradient record written by the blend backward
 constexpr int TILE_MASK_BITS = 32;    // rects of at most this many tiles get a GeomState::tile_mask from the preprocess
 constexpr uint32_t SORT_SMALL_KEYS = 4096;  // longest tile list an asynchronous forward without long_lists accepts (raster_sort.hip)
+// The two numbers an asynchronous forward takes from its descriptor for the per-tile lists, shared by the stage that uses each and
+// by s3g_raster_sort_plan: the longest list the counting kernel lets through (scan_tiles_kernel's cap_tile; 0 = the synchronous
+// forward, which checks nothing) -- the sort's launches must reach exactly that far -- and the estimate that sizes the sort's buffers.
+inline uint32_t sort_list_cap(const s3g_raster_async* as) { return as ? (as->long_lists ? 0xffffffffu : SORT_SMALL_KEYS) : 0u; }
+inline uint32_t sort_estimate(const s3g_raster_async* as) { return as->sort_lds_keys ? as->sort_lds_keys : SORT_SMALL_KEYS; }
 
 // number of binning workgroups / Gaussians per workgroup for a scene of P Gaussians
 inline int bin_blocks(int P) {

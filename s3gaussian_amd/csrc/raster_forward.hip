@@ -124,7 +124,7 @@ static int raster_forward_impl(const s3g_raster_inputs* in, const float* colors2
     // control words travel to the caller's pinned buffer behind the kernels: whoever reads them must first know that the
     // stream has passed this point (an event recorded after this call).
     R = as->capacity_instances; S = as->capacity_slots;
-    max_tile = as->sort_lds_keys ? as->sort_lds_keys : SORT_SMALL_KEYS;
+    max_tile = sort_estimate(as);
     bin_p = as->binning_arena;
     if (as->status_host)
       S3G_HIP_CHECK(hipMemcpyAsync(as->status_host, a.im.ctrl, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));

@@ -225,19 +225,18 @@ __global__ void __launch_bounds__(1024) sort_tiles_kernel(int tiles, int gx, con
   }
 }
 
-int launch_tile_sort(const Arenas& a, uint32_t* slot_map, uint32_t max_tile, const s3g_raster_async* as, hipStream_t stream, bool debug) {
-  constexpr uint32_t SMALL = SORT_SMALL_KEYS, LARGE = 16384;  // per-tile sort: lists <= SMALL in <= 32 KiB of LDS, <= LARGE in 128 KiB
-  static std::atomic<uint64_t> attr_set{0};
-  if (device_needs_setup(attr_set)) {
-    S3G_HIP_CHECK(hipFuncSetAttribute((const void*)sort_tiles_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LARGE * 8));
-    device_setup_done(attr_set);
-  }
-  // one launch over all tiles: those with lo < n <= hi sort their list (see sort_tiles_kernel for lds_keys / bucket_keys)
-  auto launch = [&](uint32_t threads, size_t lds_bytes, uint32_t lo, uint32_t hi, uint32_t lds_keys, uint32_t bucket_keys) {
-    hipLaunchKernelGGL(sort_tiles_kernel, dim3(tile_blocks(a.tiles)), dim3(threads), lds_bytes, stream, a.tiles, a.gx, a.im.ranges,
-                       a.b.keys, a.b.point_list, a.g.rect, a.g.gauss_off, slot_map, lo, hi, lds_keys, bucket_keys);
-    S3G_KERNEL_CHECK(stream, debug);
-    return S3G_OK;
+// The launches of the per-tile sort, as data: a pure host function, so that the plan can be walked list length by list length
+// without a device (s3g_raster_sort_plan, tests/test_sort_plan_cpu.py).  Every launch runs over all tiles; those with
+// lo < n <= hi sort their list (see sort_tiles_kernel for lds_keys / bucket_keys).  max_tile = the longest list: read back
+// exactly by the synchronous forward, the caller's ESTIMATE in the asynchronous one (as != NULL), where it may only size
+// buffers: every list the counting kernel lets through (sort_list_cap) must be inside exactly one launch whatever it says.
+constexpr uint32_t SORT_LARGE_KEYS = 16384;                  // lists <= SORT_SMALL_KEYS in <= 32 KiB of LDS, <= SORT_LARGE_KEYS in 128 KiB
+constexpr uint32_t SORT_MAX_LDS_BYTES = SORT_LARGE_KEYS * 8;  // hipFuncAttributeMaxDynamicSharedMemorySize of sort_tiles_kernel
+static int tile_sort_plan(uint32_t max_tile, const s3g_raster_async* as, s3g_sort_launch out[3]) {
+  constexpr uint32_t SMALL = SORT_SMALL_KEYS, LARGE = SORT_LARGE_KEYS;
+  int n = 0;
+  auto plan = [&](uint32_t threads, uint32_t lds_bytes, uint32_t lo, uint32_t hi, uint32_t lds_keys, uint32_t bucket_keys) {
+    out[n++] = s3g_sort_launch{threads, lds_bytes, lo, hi, lds_keys, bucket_keys};
   };
   // short lists: <= 32 KiB of LDS per workgroup (5 workgroups/CU); long lists: up to 128 KiB, beyond that in global
   // (asynchronous: max_tile is the caller's estimate; a list longer than the LDS buffer is sorted in global memory)
@@ -248,18 +247,60 @@ int launch_tile_sort(const Arenas& a, uint32_t* slot_map, uint32_t max_tile, con
   // round 6: lists of (BUCKET_MIN, SMALL] keys in a launch of their own with the LDS layout of bucket_sort_lds (two key buffers +
   // cursors: <= 74 KiB, two workgroups per CU); the short lists keep their small buffer and their occupancy
   const uint32_t short_cap = small_cap < BUCKET_MIN ? small_cap : BUCKET_MIN;
-  S3G_TRY(launch(256, (size_t)short_cap * 8, 0u, BUCKET_MIN, short_cap, 0u));
-  if (small_cap > BUCKET_MIN)
-    S3G_TRY(launch(SORT_THREADS_MID, (size_t)small_cap * 16 + BUCKET_LDS_EXTRA, BUCKET_MIN, SMALL, 2 * small_cap, small_cap));
+  const bool mid = small_cap > BUCKET_MIN;
+  // an estimate of <= BUCKET_MIN keys plans no medium launch, and says nothing about the lists of THIS render: the first launch
+  // then takes every list up to SMALL (those beyond its buffer run the network in global memory) instead of leaving them unsorted
+  plan(256, short_cap * 8, 0u, (as && !mid) ? SMALL : BUCKET_MIN, short_cap, 0u);
+  if (mid) plan(SORT_THREADS_MID, small_cap * 16 + BUCKET_LDS_EXTRA, BUCKET_MIN, SMALL, 2 * small_cap, small_cap);
   if (as ? as->long_lists != 0 : max_tile > SMALL) {
     // up to LARGE keys in 128 KiB: lists that fit twice (+ the cursors) take the bucket pass too, longer ones the network in LDS,
     // still longer ones the network in global memory
     const uint32_t large_cap = as ? LARGE : (max_tile < LARGE ? max_tile : LARGE);
     const uint32_t lds_bytes = large_cap * 8 > 2 * SMALL * 8 + BUCKET_LDS_EXTRA ? large_cap * 8 : 2 * SMALL * 8 + BUCKET_LDS_EXTRA;
     const uint32_t bucket_cap = (lds_bytes - BUCKET_LDS_EXTRA) / 16;
-    S3G_TRY(launch(SORT_THREADS_LONG, (size_t)lds_bytes, SMALL, 0xffffffffu, lds_bytes / 8, bucket_cap));
+    plan(SORT_THREADS_LONG, lds_bytes, SMALL, 0xffffffffu, lds_bytes / 8, bucket_cap);
+  }
+  return n;
+}
+
+int launch_tile_sort(const Arenas& a, uint32_t* slot_map, uint32_t max_tile, const s3g_raster_async* as, hipStream_t stream, bool debug) {
+  static std::atomic<uint64_t> attr_set{0};
+  if (device_needs_setup(attr_set)) {
+    S3G_HIP_CHECK(hipFuncSetAttribute((const void*)sort_tiles_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SORT_MAX_LDS_BYTES));
+    device_setup_done(attr_set);
+  }
+  s3g_sort_launch plan[3];
+  const int launches = tile_sort_plan(max_tile, as, plan);
+  for (int i = 0; i < launches; i++) {
+    const s3g_sort_launch& l = plan[i];
+    hipLaunchKernelGGL(sort_tiles_kernel, dim3(tile_blocks(a.tiles)), dim3(l.threads), (size_t)l.lds_bytes, stream, a.tiles, a.gx,
+                       a.im.ranges, a.b.keys, a.b.point_list, a.g.rect, a.g.gauss_off, slot_map, l.lo, l.hi, l.lds_keys, l.bucket_keys);
+    S3G_KERNEL_CHECK(stream, debug);
   }
   return S3G_OK;
 }
 
 }  // namespace s3g
+
+using namespace s3g;
+
+// testing hook: the plan of a forward as launch_tile_sort and launch_bin_scan would issue it; no device is touched
+extern "C" int s3g_raster_sort_plan(int asynchronous, uint32_t keys, int long_lists, s3g_sort_plan* plan) {
+  clear_error();
+  if (!plan) {
+    set_error("s3g_raster_sort_plan: NULL plan");
+    return S3G_ERR_INVALID_ARG;
+  }
+  s3g_raster_async as = {};
+  as.sort_lds_keys = keys;
+  as.long_lists = long_lists;
+  *plan = s3g_sort_plan{};
+  plan->launches = (uint32_t)tile_sort_plan(asynchronous ? sort_estimate(&as) : keys, asynchronous ? &as : nullptr, plan->launch);
+  plan->count_cap_tile = sort_list_cap(asynchronous ? &as : nullptr);
+  plan->max_lds_bytes = SORT_MAX_LDS_BYTES;
+  plan->bucket_min = BUCKET_MIN;
+  plan->small_keys = SORT_SMALL_KEYS;
+  plan->bucket_lds_extra = BUCKET_LDS_EXTRA;
+  plan->rank_direct = RANK_DIRECT;
+  return S3G_OK;
+}

@@ -45,15 +45,15 @@ class Adam(torch.optim.Adam):
         what the dropped ones would have.  Per PARAMETER: each journal entry lists the states that call advanced (a parameter
         without a gradient in a dropped iteration, or stepped in the other phase of a two-phase data-parallel step, is not touched
         for it -- ADVICE r5).  The moments and parameters were never written by the dropped launches.  -> calls taken back."""
-        n = 0
-        while self._journal and self._journal[-1][0] > step_calls:
+        # check first, mutate after: a journal that does not reach back far enough raises with every count as it was
+        n = sum(1 for calls, _ in self._journal if calls > step_calls)
+        if self.step_calls - n > step_calls:
+            raise RuntimeError(f"optim.Adam.rewind_to({step_calls}): only the last {len(self._journal)} step() calls are journalled "
+                               f"({self.step_calls} issued)")
+        for _ in range(n):
             _, states = self._journal.pop()
             for st in states:
                 st["step"] -= 1.0
-            n += 1
-        if self.step_calls - n > step_calls:
-            raise RuntimeError(f"optim.Adam.rewind_to({step_calls}): only the last {len(self._journal) + n} step() calls are journalled "
-                               f"({self.step_calls} issued)")
         self.step_calls -= n
         return n
 

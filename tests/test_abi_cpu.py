@@ -25,6 +25,8 @@ def test_library_exports_every_declared_symbol():
     L = _lib.lib()
     decl = _declared_functions()
     assert "s3g_raster_forward" in decl and "s3g_raster_backward" in decl
+    for hook in ("s3g_raster_set_bin_band", "s3g_raster_sort_plan"):       # the testing hooks are part of the declared, exported ABI
+        assert hook in decl and hook in _lib.EXPORTED_SYMBOLS
     for name in decl:
         assert hasattr(L, name), f"libs3g.so does not export {name}"
     assert L.s3g_abi_version() == _lib.ABI_VERSION

@@ -173,3 +173,38 @@ def test_adam_journal_takes_back_exactly_what_the_dropped_launches_advanced():
     launched([sa, sb])
     opt.rewind(1)
     assert (float(sa["step"]), float(sb["step"]), opt.step_calls) == (1.0, 1.0, 1)
+
+
+def test_adam_rewind_beyond_the_journal_raises_and_changes_nothing():
+    """The journal is bounded (step() keeps the last 128 .. 256 calls): a rewind_to() that asks for more than it holds cannot be
+    honoured, and must not be honoured in part -- the error leaves every state["step"], step_calls and the journal exactly as they
+    were, so that the caller still holds a consistent optimizer (the counts were taken back before the check)."""
+    import pytest
+    import torch
+    from s3gaussian_amd import optim
+    a, b = torch.nn.Parameter(torch.zeros(3)), torch.nn.Parameter(torch.zeros(3))
+    opt = optim.Adam([{"params": [a]}, {"params": [b]}], lr=0.1)
+    sa, sb = opt.state[a], opt.state[b]
+    sa["step"], sb["step"] = torch.tensor(0.0), torch.tensor(0.0)
+
+    def launched(states):
+        for st in states:
+            st["step"] += 1
+        opt.step_calls += 1
+        opt._journal.append((opt.step_calls, list(states)))
+
+    for states in ([sa, sb], [sa], [sa, sb], [sb], [sa, sb]):
+        launched(states)
+    del opt._journal[:2]                                   # what step() does to a long journal: the oldest entries are gone
+    journal = [(calls, [id(st) for st in states]) for calls, states in opt._journal]
+    for target in (0, 1):                                  # calls 1 and 2 are no longer journalled
+        with pytest.raises(RuntimeError, match="only the last 3 step"):
+            opt.rewind_to(target)
+        assert (float(sa["step"]), float(sb["step"]), opt.step_calls) == (4.0, 4.0, 5)
+        assert [(calls, [id(st) for st in states]) for calls, states in opt._journal] == journal
+    with pytest.raises(RuntimeError):
+        opt.rewind(5)
+    assert (float(sa["step"]), float(sb["step"]), opt.step_calls, len(opt._journal)) == (4.0, 4.0, 5, 3)
+    # as far back as the journal reaches is still honoured, per parameter
+    assert opt.rewind_to(2) == 3 and (float(sa["step"]), float(sb["step"]), opt.step_calls, opt._journal) == (2.0, 1.0, 2, [])
+    assert opt.rewind_to(2) == 0 and opt.rewind_to(7) == 0 and opt.step_calls == 2

@@ -64,6 +64,80 @@ def test_async_forward_is_bit_identical_to_the_synchronous_one(gpu_device, P, W,
     assert st["overflows"] == [] and st["mean_instances"] > 0
 
 
+def _clump_scenes(K):
+    """Scene A: 300 Gaussians spread over a 64 x 64 image, no tile list of more than 128 instances.  Scene B: A plus a clump of K
+    small faint Gaussians (the one-tile scene of tests/test_tile_sort_gpu.py) moved from the middle of the image -- a tile corner at
+    this size -- to the middle of tile (2, 2): pixel 39.5 = NDC 0.25, so that ONE list grows by K while every other stays as it was."""
+    A = tiny_scene(P=300, W=64, H=64)
+    c = tiny_scene(P=K, W=64, H=64, seed=K % 97 + 3, scale=0.004, sigma=0.1, spread=0.05)
+    c["opacities"] = c["opacities"] * 0.01 + 0.005            # low opacity: transmittance survives the whole clump
+    c["means3D"][:, :2] += 0.25 * A["cam"]["tanfovx"] * c["means3D"][:, 2:3]
+    B = dict(A)
+    for k in ("means3D", "scales", "rotations", "opacities", "shs", "colors_precomp"):
+        B[k] = torch.cat([A[k], c[k]], 0).contiguous()
+    return A, B
+
+
+def _sync_counts(s, dev):
+    """(instances, longest tile list) of a scene from the control words of a SYNCHRONOUS forward."""
+    from diff_gaussian_rasterization import _C
+    from s3gaussian_amd import _debug
+    cam = s["cam"]
+    e = torch.Tensor([])
+    d = lambda k: s[k].to(dev).contiguous()
+    R, _color, _depth, _radii, _geom, _binning, img = _C.rasterize_gaussians(
+        s["bg"].to(dev), d("means3D"), d("colors_precomp"), d("opacities"), d("scales"), d("rotations"), 1.0, e,
+        cam["viewmatrix"].to(dev), cam["projmatrix"].to(dev), cam["tanfovx"], cam["tanfovy"], cam["image_height"], cam["image_width"],
+        e, 0, cam["campos"].to(dev), False, False)
+    ctrl = _debug.decode_image(img, cam["image_width"], cam["image_height"])["ctrl"].tolist()
+    assert ctrl[0] == R
+    return R, ctrl[1]
+
+
+@pytest.mark.parametrize("K", [600, 3000])
+@pytest.mark.parametrize("pair", [False, True])
+@pytest.mark.parametrize("policy", ["verified", "speculative"])
+def test_a_list_that_outgrows_the_sort_estimate_is_still_sorted(gpu_device, policy, pair, K):
+    """The estimate of the longest tile list (_AsyncState.caps -> s3g_raster_async.sort_lds_keys) comes from EARLIER renders of the
+    image size.  Here it is learnt on scene A (no list above 128 instances: 256 keys, no long-list pass) and then meets scene B, one
+    tile of which holds K more -- another camera, a densification.  Nothing overflows (the instance capacity is far away), so neither
+    policy is told anything: the render has to be right as it is, bit for bit the synchronous one, gradients included."""
+    from s3gaussian_amd import raster_C
+    dev = gpu_device
+    key = (64, 64)
+    A, B = _clump_scenes(K)
+    prev = raster_C.set_async(True)
+    prev_policy = raster_C.set_async_policy(policy)
+    try:
+        raster_C._async_states.pop(dev.index or 0, None)                   # a fresh history: scene A is all it will know
+        raster_C.invalidate_geometry_cache()
+        _render_and_grads(A, dev, pair)
+        st = raster_C._async_state(dev)
+        st.drain(block=True)
+        longest_A = st.hist[key][2]
+        assert 0 < longest_A <= 128 and st.caps(key)[2:] == (256, 0)
+        calls, reissued = st.seq, st.reissued
+        raster_C.invalidate_geometry_cache()
+        o_async, g_async = _render_and_grads(B, dev, pair)
+        st.drain(block=True)
+        assert st.seq == calls + 1 and st.reissued == reissued and st.overflows == []      # issued once, with the stale estimate
+        row = st.status_host[calls % raster_C._ASYNC_RING].tolist()
+        assert row[4] == 0 and 512 < row[1] <= 4096 and 0 < row[5] == row[0] < st.caps(key)[0]
+        raster_C.set_async(False)
+        raster_C.invalidate_geometry_cache()
+        o_sync, g_sync = _render_and_grads(B, dev, pair)
+        n_sync, longest_sync = _sync_counts(B, dev)                       # the synchronous forward's own control words
+        assert 512 < longest_sync <= 4096 and (n_sync, longest_sync) == (row[0], row[1]) and _sync_counts(A, dev)[1] == longest_A
+        for a, b in zip(o_sync + g_sync, o_async + g_async):
+            assert torch.equal(a, b)
+        assert float(g_sync[2][300:].abs().max()) > 0                      # the clump's opacities have a gradient: it was blended
+    finally:
+        raster_C.set_async(prev)
+        raster_C.set_async_policy(prev_policy)
+        raster_C._async_states.pop(dev.index or 0, None)                   # forget the history of these two scenes
+        raster_C.invalidate_geometry_cache()
+
+
 def test_overflow_is_a_device_side_no_op_and_is_reported_late(gpu_device, monkeypatch):
     """Shrink the capacity policy so that the next forward cannot hold its instances: image = background, gradients = 0, the
     densification accumulators and (through the guarded Adam step) the parameters stay untouched; the report arrives at a later
