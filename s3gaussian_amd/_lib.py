@@ -56,6 +56,17 @@ class SortPlan(C.Structure):
                 ("bucket_min", C.c_uint32), ("small_keys", C.c_uint32), ("bucket_lds_extra", C.c_uint32), ("rank_direct", C.c_uint32)]
 
 
+class SkyCamera(C.Structure):
+    """struct s3g_skymodel_camera (include/s3g_skymodel.h): host doubles."""
+    _fields_ = [("R", C.c_double * 9), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class SkyExtents(C.Structure):
+    """struct s3g_skymodel_extents (include/s3g_skymodel.h): what s3g_skymodel_plan decides."""
+    _fields_ = [("tile_pixels", C.c_int), ("tiles", C.c_int), ("band_pixels", C.c_int), ("bands", C.c_int), ("chunks", C.c_int),
+                ("reserved", C.c_int), ("workspace_bytes", C.c_size_t)]
+
+
 def build(force: bool = False) -> str:
     """Compile every HIP source for gfx950 into s3gaussian_amd/lib/libs3g.so (in-tree, travels with gpurun)."""
     cmd = ["make", "-s", "-C", CSRC_DIR, "-j8"] + (["-B"] if force else [])
@@ -135,6 +146,19 @@ def lib() -> C.CDLL:
     L.s3g_pose_apply.argtypes = [vp] * 7
     L.s3g_pose_apply_backward.restype = C.c_int
     L.s3g_pose_apply_backward.argtypes = [vp] * 6
+    # include/s3g_skymodel.h: the sky colour model
+    L.s3g_skymodel_tile_pixels.restype = C.c_int
+    L.s3g_skymodel_tile_pixels.argtypes = []
+    L.s3g_skymodel_plan.restype = C.c_int
+    L.s3g_skymodel_plan.argtypes = [C.c_longlong, C.c_int, C.POINTER(SkyExtents)]
+    L.s3g_skymodel_pack_bytes.restype = C.c_size_t
+    L.s3g_skymodel_pack_bytes.argtypes = []
+    L.s3g_sky_pack.restype = C.c_int
+    L.s3g_sky_pack.argtypes = [vp] * 8
+    L.s3g_sky_forward.restype = C.c_int
+    L.s3g_sky_forward.argtypes = [C.c_int, C.c_int, C.POINTER(SkyCamera), vp, vp, vp, vp, vp]
+    L.s3g_sky_backward.restype = C.c_int
+    L.s3g_sky_backward.argtypes = [C.c_int, C.c_int, C.POINTER(SkyCamera), vp, vp, vp, C.c_int, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -195,4 +219,4 @@ def check(code: int) -> None:
         raise RuntimeError(f"libs3g error {code}: {msg}")
 
 
-EXPORTED_SYMBOLS = ["s3g_raster_forward", "s3g_raster_forward_reuse", "s3g_raster_forward_decompose", "s3g_raster_forward2", "s3g_raster_forward_async", "s3g_raster_arena_bytes", "s3g_adam_step_guarded", "s3g_raster_backward", "s3g_raster_backward_workspace_bytes", "s3g_raster_backward2", "s3g_raster_backward2_workspace_bytes", "s3g_hexplane_forward_workspace_bytes", "s3g_knn_workspace_bytes", "s3g_knn_mean_dist2", "s3g_hexplane_forward", "s3g_hexplane_backward", "s3g_hexplane_backward_algo", "s3g_hexplane_backward_workspace_bytes", "s3g_hexplane_backward_scratch_rows", "s3g_hexplane_debug_walk_mask", "s3g_hexplane_set_deterministic", "s3g_hexplane_get_deterministic", "s3g_hexplane_sort_state_words", "s3g_profile_enable", "s3g_profile_read", "s3g_ssim_forward", "s3g_ssim_backward", "s3g_plane_regulation", "s3g_scale_unless_one", "s3g_pixel_losses_forward", "s3g_pixel_losses_combine", "s3g_pixel_losses_combine_views", "s3g_pixel_losses_backward", "s3g_photometric_forward", "s3g_photometric_backward", "s3g_glue_forward", "s3g_glue_backward", "s3g_glue_forward_views", "s3g_glue_backward_views", "s3g_deform_mlp_forward", "s3g_deform_mlp_backward", "s3g_deform_mlp_backward_ordered", "s3g_deform_mlp_wgrad_partial_bytes", "s3g_deform_mlp_stash_bytes", "s3g_deform_mlp_pack_bytes", "s3g_deform_mlp_set_arithmetic", "s3g_deform_mlp_get_arithmetic", "s3g_deform_infer", "s3g_deform_infer_split", "s3g_deform_infer_workspace_bytes", "s3g_deform_infer_heads_lds_bytes", "s3g_deform_infer_heads", "s3g_deform_geom_stash_bytes", "s3g_deform_geom_workspace_bytes", "s3g_deform_geom_forward", "s3g_deform_geom_backward", "s3g_adam_step", "s3g_densify_stats", "s3g_densify_stats_guarded", "s3g_densify_stats_views", "s3g_densify_stats_views_guarded", "s3g_density_count_words", "s3g_density_classify_densify", "s3g_density_classify_prune", "s3g_density_scan", "s3g_density_apply", "s3g_density_reset_opacity", "s3g_image_metrics_workspace_bytes", "s3g_image_metrics", "s3g_scene_flow_workspace_bytes", "s3g_scene_flow_colors", "s3g_frame_workspace_bytes", "s3g_frame_tiles", "s3g_depthvis_workspace_bytes", "s3g_depth_percentiles", "s3g_depth_colors", "s3g_depth_turbo_table", "s3g_split_count_words", "s3g_split_workspace_bytes", "s3g_split_classify", "s3g_split_mask_offsets", "s3g_split_pack_rows", "s3g_lidar_depth_workspace_bytes", "s3g_lidar_depth_maps", "s3g_lidar_count_words", "s3g_lidar_cloud_add", "s3g_lidar_grid_workspace_bytes", "s3g_lidar_grid_range", "s3g_lidar_grid_keys", "s3g_lidar_grid_heads", "s3g_lidar_grid_gather", "s3g_lpips_weights_bytes", "s3g_lpips_pack_weights", "s3g_lpips_workspace_bytes", "s3g_lpips", "s3g_lpips_vgg_weights_bytes", "s3g_lpips_vgg_pack_weights", "s3g_lpips_vgg_workspace_bytes", "s3g_lpips_vgg", "s3g_raster_backward_accum", "s3g_raster_backward2_accum", "s3g_raster_alpha", "s3g_raster_backward_alpha", "s3g_sky_loss_workspace_bytes", "s3g_sky_loss", "s3g_camera_backward_workspace_bytes", "s3g_camera_backward", "s3g_pose_apply", "s3g_pose_apply_backward", "s3g_mark_visible", "s3g_raster_set_exact_cull", "s3g_raster_get_exact_cull", "s3g_raster_set_bin_band", "s3g_raster_sort_plan", "s3g_raster_set_backward_wave_bounds", "s3g_last_error", "s3g_abi_version"]
+EXPORTED_SYMBOLS = ["s3g_raster_forward", "s3g_raster_forward_reuse", "s3g_raster_forward_decompose", "s3g_raster_forward2", "s3g_raster_forward_async", "s3g_raster_arena_bytes", "s3g_adam_step_guarded", "s3g_raster_backward", "s3g_raster_backward_workspace_bytes", "s3g_raster_backward2", "s3g_raster_backward2_workspace_bytes", "s3g_hexplane_forward_workspace_bytes", "s3g_knn_workspace_bytes", "s3g_knn_mean_dist2", "s3g_hexplane_forward", "s3g_hexplane_backward", "s3g_hexplane_backward_algo", "s3g_hexplane_backward_workspace_bytes", "s3g_hexplane_backward_scratch_rows", "s3g_hexplane_debug_walk_mask", "s3g_hexplane_set_deterministic", "s3g_hexplane_get_deterministic", "s3g_hexplane_sort_state_words", "s3g_profile_enable", "s3g_profile_read", "s3g_ssim_forward", "s3g_ssim_backward", "s3g_plane_regulation", "s3g_scale_unless_one", "s3g_pixel_losses_forward", "s3g_pixel_losses_combine", "s3g_pixel_losses_combine_views", "s3g_pixel_losses_backward", "s3g_photometric_forward", "s3g_photometric_backward", "s3g_glue_forward", "s3g_glue_backward", "s3g_glue_forward_views", "s3g_glue_backward_views", "s3g_deform_mlp_forward", "s3g_deform_mlp_backward", "s3g_deform_mlp_backward_ordered", "s3g_deform_mlp_wgrad_partial_bytes", "s3g_deform_mlp_stash_bytes", "s3g_deform_mlp_pack_bytes", "s3g_deform_mlp_set_arithmetic", "s3g_deform_mlp_get_arithmetic", "s3g_deform_infer", "s3g_deform_infer_split", "s3g_deform_infer_workspace_bytes", "s3g_deform_infer_heads_lds_bytes", "s3g_deform_infer_heads", "s3g_deform_geom_stash_bytes", "s3g_deform_geom_workspace_bytes", "s3g_deform_geom_forward", "s3g_deform_geom_backward", "s3g_adam_step", "s3g_densify_stats", "s3g_densify_stats_guarded", "s3g_densify_stats_views", "s3g_densify_stats_views_guarded", "s3g_density_count_words", "s3g_density_classify_densify", "s3g_density_classify_prune", "s3g_density_scan", "s3g_density_apply", "s3g_density_reset_opacity", "s3g_image_metrics_workspace_bytes", "s3g_image_metrics", "s3g_scene_flow_workspace_bytes", "s3g_scene_flow_colors", "s3g_frame_workspace_bytes", "s3g_frame_tiles", "s3g_depthvis_workspace_bytes", "s3g_depth_percentiles", "s3g_depth_colors", "s3g_depth_turbo_table", "s3g_split_count_words", "s3g_split_workspace_bytes", "s3g_split_classify", "s3g_split_mask_offsets", "s3g_split_pack_rows", "s3g_lidar_depth_workspace_bytes", "s3g_lidar_depth_maps", "s3g_lidar_count_words", "s3g_lidar_cloud_add", "s3g_lidar_grid_workspace_bytes", "s3g_lidar_grid_range", "s3g_lidar_grid_keys", "s3g_lidar_grid_heads", "s3g_lidar_grid_gather", "s3g_lpips_weights_bytes", "s3g_lpips_pack_weights", "s3g_lpips_workspace_bytes", "s3g_lpips", "s3g_lpips_vgg_weights_bytes", "s3g_lpips_vgg_pack_weights", "s3g_lpips_vgg_workspace_bytes", "s3g_lpips_vgg", "s3g_raster_backward_accum", "s3g_raster_backward2_accum", "s3g_raster_alpha", "s3g_raster_backward_alpha", "s3g_sky_loss_workspace_bytes", "s3g_sky_loss", "s3g_camera_backward_workspace_bytes", "s3g_camera_backward", "s3g_pose_apply", "s3g_pose_apply_backward", "s3g_skymodel_tile_pixels", "s3g_skymodel_plan", "s3g_skymodel_pack_bytes", "s3g_sky_pack", "s3g_sky_forward", "s3g_sky_backward", "s3g_mark_visible", "s3g_raster_set_exact_cull", "s3g_raster_get_exact_cull", "s3g_raster_set_bin_band", "s3g_raster_sort_plan", "s3g_raster_set_backward_wave_bounds", "s3g_last_error", "s3g_abi_version"]

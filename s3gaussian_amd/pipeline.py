@@ -148,6 +148,23 @@ class GaussianParams(nn.Module):
             self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
         return self.optimizer
 
+    def attach_sky_model(self, model, lr: float = 0.0025):
+        """Adds the sky colour model's six parameters to `self.optimizer` as ONE param group named "sky_model" (lr: the reference's
+        bg_model_lr), after training_setup.  The group then shares the optimizer's overflow guard, its rewind under
+        run_training_steps and the data-parallel reducers; density control skips it (a multi-parameter group).  The model is moved to
+        the Gaussians' device; it does not become a submodule (checkpoints of the Gaussians keep their keys)."""
+        from . import skymodel as _skymodel
+        opt = getattr(self, "optimizer", None)
+        if opt is None:
+            raise RuntimeError("attach_sky_model: call training_setup first (there is no optimizer to add the group to)")
+        if any(g.get("name") == "sky_model" for g in opt.param_groups):
+            raise RuntimeError('attach_sky_model: the optimizer already has a "sky_model" group')
+        if not isinstance(model, _skymodel.SkyModel):
+            raise TypeError("attach_sky_model: an s3gaussian_amd.skymodel.SkyModel")
+        model.to(self._xyz.device)
+        opt.add_param_group({"params": model.tensors(), "lr": float(lr), "name": "sky_model"})
+        return model
+
     # ---- adaptive density control (density.py; the reference's argument order, its unused trailing arguments accepted and ignored) ----
     def densify(self, max_grad, min_opacity, extent, max_screen_size, density_threshold=None, displacement_scale=None,
                 model_path=None, iteration=None, stage=None, **kw):
@@ -516,9 +533,33 @@ def _view_result(image, means2D, radii, depth, image2, alpha, want_feat, return_
     return out
 
 
+def _sky_refusals(where: str, sky_model, pose=None, override_color=None) -> None:
+    """What a sky model does not go together with, refused by name."""
+    if pose is not None:
+        raise RuntimeError(f"{where}(sky_model=..., pose=...): the refined pose lives on the device, the sky model's directions take "
+                           "host camera values; render the sky model without pose refinement")
+    if override_color is not None:
+        raise RuntimeError(f"{where}(sky_model=..., override_color=...): an override colour is not a radiance the sky is composited behind")
+
+
+def _sky_attached(where: str, pc, sky_model) -> None:
+    from . import skymodel as _skymodel
+    if _skymodel.attached_group(getattr(pc, "optimizer", None), sky_model) is None:
+        raise RuntimeError(f'{where}(sky_model=...): the model is not attached: pc.attach_sky_model(model) adds its "sky_model" '
+                           "param group to pc.optimizer")
+
+
+def _sky_compose(out: Dict, sky_model, cam: Dict) -> Dict:
+    """out["render"] <- out["render"] + (1 - out["alpha"]) * sky; the render over black stays as out["render_fg"]."""
+    from . import skymodel as _skymodel
+    out["render_fg"] = out["render"]
+    out["render"] = _skymodel.sky_composite(sky_model, cam, out["render_fg"], out["alpha"])
+    return out
+
+
 def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torch.Tensor,
            scaling_modifier=1.0, override_color=None, stage="fine", return_decomposition=False, return_dx=False,
-           render_feat=False, densify_accum=None, extra_colors=None, return_alpha=False, pose=None, cam_index=None):
+           render_feat=False, densify_accum=None, extra_colors=None, return_alpha=False, pose=None, cam_index=None, sky_model=None):
     """Mirror of gaussian_renderer/__init__.py::render.  `viewpoint_camera` is a dict with the fields the reference
     reads from a Camera (image_height/width, FoVx/FoVy or tanfovx/tanfovy, world_view_transform=viewmatrix,
     full_proj_transform=projmatrix, camera_center=campos, time).
@@ -532,7 +573,18 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
     return_alpha (extension): out["alpha"] = the accumulated opacity [1,H,W] of the main render, 1 - the final transmittance of
     each pixel (rasterizer.forward_alpha); differentiable, zeros for a model without Gaussians.  False launches nothing new.
     pose (extension): a pose.PoseRefiner; the camera is then rendered at its refined pose, pose.corrected(camera, cam_index), and
-    under autograd the loss back-propagates to the refiner's correction of that camera.  None launches nothing new."""
+    under autograd the loss back-propagates to the refiner's correction of that camera.  None launches nothing new.
+    sky_model (extension): a skymodel.SkyModel on the Gaussians' device.  Implies return_alpha; the Gaussians are rendered over a
+    ZERO background of the call's own and `bg_color` is NOT used.  out["render"] = render_fg + (1 - alpha) * sky is the composite
+    (skymodel.sky_composite, differentiable w.r.t. the model, the render and the opacity), out["render_fg"] the Gaussians over
+    black, out["alpha"] the opacity image; the decomposition's render_d / render_s and out["extra"] stay over black.  Refused
+    together with pose= and with override_color.  The directions take the camera's rotation as host values: with `viewmatrix` on
+    the device that is one blocking read-back per call (the host waits for the rasterizer forward); a camera dict that also carries
+    "viewmatrix_host", a CPU copy of viewmatrix, avoids it (skymodel.camera_intrinsics).  None launches nothing new."""
+    if sky_model is not None:
+        _sky_refusals("render", sky_model, pose, override_color)
+        bg_color = torch.zeros(3, dtype=torch.float32, device=pc.get_xyz.device)
+        return_alpha = True
     if pose is not None:
         if cam_index is None:
             raise RuntimeError("render(pose=...): cam_index says which of the refiner's cameras this is")
@@ -653,6 +705,8 @@ def render(viewpoint_camera: Dict, pc: GaussianParams, pipe: SimpleNamespace, bg
             extra.append(rasterizer(means3D=means3D_final, means2D=means2D, shs=None, colors_precomp=c, opacities=opacity,
                                     scales=scales_final, rotations=rotations_final, cov3D_precomp=cov3D_precomp)[0])
         out["extra"] = extra
+    if sky_model is not None:
+        _sky_compose(out, sky_model, cam)
     return out
 
 
@@ -703,7 +757,7 @@ def psnr(img1, img2):
 
 
 def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: torch.Tensor, masks=None, stage="fine",
-             return_decomposition=False, lpips=None, pose=None) -> Dict:
+             return_decomposition=False, lpips=None, pose=None, sky_model=None) -> Dict:
     """The metric part of the reference's evaluation loop (utils/video_utils.py:169-241, 301-307): every camera is rendered under
     no_grad, frame i's {psnr, ssim, masked_psnr, masked_ssim, masked_pixels} goes into row i of one [N,5] device tensor
     (metrics.image_metrics), and that tensor is read back ONCE after the last frame.  masks: None, or one entry per camera (None
@@ -716,7 +770,11 @@ def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: 
     (non_zero_mean of the totals, utils/video_utils.py:210, 305) and "lpips_per_frame" ([N,6] float64 on the host), the same keys
     for either model.  Without a model nothing changes.
     pose: None, or a pose.PoseRefiner with one row per camera: camera i is rendered at pose.corrected(camera, i) (training views at
-    their refined poses; no gradient flows here)."""
+    their refined poses; no gradient flows here).
+    sky_model: None, or a skymodel.SkyModel: every frame is render(sky_model=...)'s composite and the metrics are computed on it
+    (`bg` is then not used); refused together with pose=."""
+    if sky_model is not None:
+        _sky_refusals("evaluate", sky_model, pose)
     n = len(cameras)
     if len(gt_images) != n or (masks is not None and len(masks) != n):
         raise RuntimeError("evaluate: one ground-truth image (and one mask entry) per camera")
@@ -725,7 +783,8 @@ def evaluate(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: 
     with torch.no_grad():
         for i, cam in enumerate(cameras):
             pkg = render(cam, pc, pipe, bg, stage=stage, return_decomposition=return_decomposition,
-                         **({"pose": pose, "cam_index": i} if pose is not None else {}))
+                         **({"pose": pose, "cam_index": i} if pose is not None else {}),
+                         **({"sky_model": sky_model} if sky_model is not None else {}))
             _metrics.image_metrics(pkg["render"], gt_images[i], None if masks is None else masks[i], out=table[i])
             if lpips is not None:
                 lpips_fn(lpips, pkg["render"], gt_images[i], out=lpips_table[i])
@@ -779,7 +838,8 @@ def _fused_route_missing(pc: GaussianParams, pipe: SimpleNamespace) -> str:
 
 @torch.no_grad()
 def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.Tensor, num_cams: int = 3, sink=None,
-                 with_rgb: bool = False, return_decomposition: bool = False, on_frame=None, return_alpha: bool = False) -> Dict:
+                 with_rgb: bool = False, return_decomposition: bool = False, on_frame=None, return_alpha: bool = False,
+                 sky_model=None) -> Dict:
     """The forward and backward scene-flow images of the reference's evaluation loop (utils/video_utils.py:203-209, 252-299): frame t,
     rendered in stage "fine" at its own camera and time, painted with C(dx[t + n] - dx[t]) and C(dx[t] - dx[t - n]) (flow.frame_plan,
     n = num_cams; C = flow.scene_flow_colors).  `cameras` in dataset order: num_cams cameras per timestamp.
@@ -800,6 +860,8 @@ def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.T
     return_decomposition and return_alpha are passed on to each frame's render(); on_frame(i, pkg) is called with frame i's full render result (its
     "extra" holds the forward flow image first and the backward one last) before the images are delivered: evaluate_video hangs the
     rest of the evaluation on the same render this way.
+    sky_model: each frame's render(sky_model=...): "rgbs" (and on_frame's pkg["render"]) are the composite; the flow images stay
+    over black and `bg` is not used.
     Needs the fused deformation route (the reference's default head configuration, SH degree 3, on the GPU): there is no second
     implementation behind it."""
     from . import flow as _flow
@@ -840,7 +902,8 @@ def render_flows(pc: GaussianParams, cameras, pipe: SimpleNamespace, bg: torch.T
                 colors[pair] = _flow.scene_flow_colors(window[pair[0]], window[pair[1]])
         unique = [colors[pairs[0]]] + ([colors[pairs[1]]] if pairs[1] != pairs[0] else [])
         pkg = render(cam, pc, pipe, bg, stage="fine", return_decomposition=return_decomposition, extra_colors=unique,
-                     **({"return_alpha": True} if return_alpha else {}))
+                     **({"return_alpha": True} if return_alpha else {}),
+                     **({"sky_model": sky_model} if sky_model is not None else {}))
         if on_frame is not None:
             on_frame(i, pkg)
         if with_rgb:
@@ -937,7 +1000,7 @@ _VIDEO_ONE_CHANNEL = ("depths", "opacities")
 def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace, bg: torch.Tensor, masks=None, num_cams: int = 3,
                    keys=("gt_rgbs", "rgbs", "depths", "dynamic_rgbs", "static_rgbs"), sink=None, host: bool = False,
                    compute_metrics: bool = True, stage: str = "fine", lpips=None, sky_keys=(), sky_masks=None, depth_keys=(),
-                   depth_bounds=(4.0, 120.0), pose=None) -> Dict:
+                   depth_bounds=(4.0, 120.0), pose=None, sky_model=None) -> Dict:
     """The reference's evaluation loop with its videos' frames (utils/video_utils.py:116-349 render_func, then 439-499
     save_seperate_videos) from ONE render per camera: render(cam, return_decomposition=<a decomposition key is asked for>,
     extra_colors=<the frame's flow colours, if a flow key is asked for>) feeds metrics.image_metrics -- row i of the [N,5] table,
@@ -972,9 +1035,14 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     lpips: None, or an LPIPS (AlexNet) or LPIPSVGG (VGG16) model: as in evaluate(), the result gains "lpips" and "lpips_per_frame" (it needs
     compute_metrics=True).
     Flow keys run the loop through render_flows (its windowing of dx and colours; stage "fine", at least 2 * num_cams cameras); they
-    and the decomposition keys need the fused deformation route, as render_flows does."""
+    and the decomposition keys need the fused deformation route, as render_flows does.
+    sky_model: None, or a skymodel.SkyModel: every frame is render(sky_model=...); the metrics and the "rgbs" strips are computed on
+    the composite (the decomposition and flow strips stay over black; `bg` is not used).  Refused together with pose=."""
     from . import depthvis as _depthvis
     from . import frames as _frames
+    if sky_model is not None:
+        _sky_refusals("evaluate_video", sky_model, pose)
+    sky_kw = {"sky_model": sky_model} if sky_model is not None else {}
     keys, sky_keys, depth_keys = tuple(keys), tuple(sky_keys), tuple(depth_keys)
     unknown = [k for k in keys if k not in VIDEO_KEYS]
     if unknown or not (keys or sky_keys or depth_keys) or len(set(keys)) != len(keys) or len(keys) > _frames.MAX_JOBS:
@@ -1102,11 +1170,11 @@ def evaluate_video(pc: GaussianParams, cameras, gt_images, pipe: SimpleNamespace
     with torch.no_grad():
         if want_flow:
             render_flows(pc, cameras, pipe, bg, num_cams=n, sink=lambda kind, i, image: None, return_decomposition=want_dec,
-                         on_frame=on_frame, **({"return_alpha": True} if want_alpha else {}))
+                         on_frame=on_frame, **({"return_alpha": True} if want_alpha else {}), **sky_kw)
         else:
             for i, cam in enumerate(cameras):
                 on_frame(i, render(cam, pc, pipe, bg, stage=stage, return_decomposition=want_dec,
-                                   **({"return_alpha": True} if want_alpha else {})))
+                                   **({"return_alpha": True} if want_alpha else {}), **sky_kw))
         drain(state.pending)
     if not compute_metrics:
         result.update({"psnr": -1, "ssim": -1, "masked_psnr": -1, "masked_ssim": -1, "per_frame": None})
@@ -1252,7 +1320,7 @@ def _finish_step(pc: GaussianParams, pkgs, grad_hook, optimizer_step) -> None:
 
 def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hyper, opt, bg, stage="fine",
                   pipe: Optional[SimpleNamespace] = None, grad_hook=None, densify_stats=False, optimizer_step=None, sky_mask=None,
-                  pose=None, cam_index=None):
+                  pose=None, cam_index=None, sky_model=None):
     """One iteration of train.py for one view: render -> loss -> backward -> Adam step.  `grad_hook(pc, pkg)` runs
     between backward and the optimizer step (used by the data-parallel wrapper for the RCCL all-reduce).
     densify_stats=True also does the bookkeeping of train.py:489-493 (max_radii2D, xyz_gradient_accum, denom) for this
@@ -1265,8 +1333,14 @@ def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hy
     lambda_sky * sky.sky_opacity_loss; its gradient rides in the same rasterizer backward, fused densify statistics included.
     Without a mask, or with lambda_sky = 0, nothing new is launched.
     pose (extension): a pose.PoseRefiner with cam_index = this camera's row in it: the view is rendered at its refined pose and
-    the refiner's optimizer steps and clears beside the model's.  Not under the data-parallel wrapper.  None: nothing new."""
+    the refiner's optimizer steps and clears beside the model's.  Not under the data-parallel wrapper.  None: nothing new.
+    sky_model (extension): a skymodel.SkyModel attached with pc.attach_sky_model: the loss sees render(sky_model=...)'s composite,
+    the composite's gradient on the opacity image adds to the sky-mask term's inside the one rasterizer backward, and the model's
+    gradients are stepped by pc.optimizer ("sky_model" group).  `bg` is then not used.  Refused with pose=.  None: nothing new."""
     pipe = _default_pipe(pipe)
+    if sky_model is not None:
+        _sky_refusals("training_step", sky_model, pose)
+        _sky_attached("training_step", pc, sky_model)
     if pose is not None:
         from . import dp as _dp
         if _dp.active():
@@ -1275,7 +1349,8 @@ def training_step(pc: GaussianParams, cam: Dict, gt_image, gt_depth, gt_feat, hy
     want_sky = _sky_weight(opt, sky_mask) != 0.0
     pkg = render(cam, pc, pipe, bg, stage=stage, return_dx=True, render_feat=(stage == "fine" and hyper.feat_head),
                  densify_accum=acc, **({"return_alpha": True} if want_sky else {}),
-                 **({"pose": pose, "cam_index": cam_index} if pose is not None else {}))
+                 **({"pose": pose, "cam_index": cam_index} if pose is not None else {}),
+                 **({"sky_model": sky_model} if sky_model is not None else {}))
     loss = training_loss(pc, pkg, gt_image, gt_depth, gt_feat, hyper, opt, stage, **({"sky_mask": sky_mask} if want_sky else {}))
     loss.backward()
     if densify_stats and not pkg.get("densify_stats_fused", False):
@@ -1308,9 +1383,12 @@ def rig_batches(cameras, num_cams: int = 3):
     return out
 
 
-def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation, return_alpha=False):
+def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation, return_alpha=False, sky_model=None):
     """-> (result dicts, the skip word of each view's asynchronous forward or None)."""
     from . import raster_C
+    if sky_model is not None:      # as in render(): a zero background of the call's own, the opacity image, the composite per view
+        bg_color = torch.zeros(3, dtype=torch.float32, device=pc.get_xyz.device)
+        return_alpha = True
     from .glue import MAX_VIEWS, activations_and_colors_views
     V = len(cams)
     if torch.is_grad_enabled() and any(torch.is_tensor(cam.get(k)) and cam[k].requires_grad
@@ -1327,7 +1405,8 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
         outs, words = [], []
         for cam, f in zip(cams, flags):     # the library route: nothing to share, the same results contract
             outs.append(render(cam, pc, pipe, bg_color, stage=stage, return_dx=return_dx, render_feat=f,
-                               **({"return_alpha": True} if return_alpha else {})))
+                               **({"return_alpha": True} if return_alpha else {}),
+                               **({"sky_model": sky_model} if sky_model is not None else {})))
             words.append(raster_C.async_skip_flag(dev) if dev.type == "cuda" else None)
         return outs, words
     groups: Dict[float, list] = {}
@@ -1360,11 +1439,13 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
             words[i] = raster_C.async_skip_flag(dev)
             outs[i] = _view_result(image, means2D, radii, depth, image2, alpha, want_feat, return_alpha, return_dx and "fine" in stage,
                                    dx, dshs, dshs_l1, plane_reg)
+            if sky_model is not None:
+                _sky_compose(outs[i], sky_model, cams[i])
     return outs, words
 
 
 def render_views(cams, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torch.Tensor, stage="fine", render_feat=False,
-                 return_dx=True, share_deformation=True, return_alpha=False):
+                 return_dx=True, share_deformation=True, return_alpha=False, sky_model=None):
     """render() for a batch of views -> a list of result dicts with the keys render() returns, in the order of `cams`.
     The deformation field depends on (xyz, t) only, never on the camera.  On the fused route (stage "coarse", or a network on
     Deformation._fused_any with the fused glue: every head subset, no_dx, the geometry heads) the views are grouped by cam["time"]
@@ -1379,8 +1460,10 @@ def render_views(cams, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torc
     compute_cov3D_python) this is one render() per view: same contract, nothing shared.
     No densify_accum here: a batch's densification statistics take the norm of the summed viewspace gradient
     (optim.densify_stats_views), which a per-view update inside the rasterizer's backward cannot give.
-    return_alpha: every dict carries "alpha", as render(return_alpha=True) gives it."""
-    return _render_views(list(cams), pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation, bool(return_alpha))[0]
+    return_alpha: every dict carries "alpha", as render(return_alpha=True) gives it.
+    sky_model: every view as render(sky_model=...) gives it ("render" the composite, "render_fg", "alpha"); bg_color is not used."""
+    return _render_views(list(cams), pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation, bool(return_alpha),
+                         sky_model)[0]
 
 
 def _supervised_feat_views(V: int, hyper, stage: str, feat_views: str):
@@ -1430,7 +1513,7 @@ def training_loss_views(pc: GaussianParams, pkgs, gt_images, gt_depths, gt_feats
 
 def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats, hyper, opt, bg, stage="fine",
                         pipe: Optional[SimpleNamespace] = None, grad_hook=None, densify_stats=False, optimizer_step=None,
-                        feat_views="last", share_deformation=True, sky_masks=None):
+                        feat_views="last", share_deformation=True, sky_masks=None, sky_model=None):
     """One iteration of train.py for a batch of V views (opt.batch_size = V, train.py:365-437, 489-493, 521-522): V renders -> one
     loss (training_loss_views: the reference's batch semantics) -> one backward -> ONE Adam step.  -> (loss, result dicts).
     Views that share a timestamp (a rig's cameras of one frame) share one deformation pass and one glue pass each way
@@ -1440,7 +1523,8 @@ def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats
     share_deformation=False evaluates the field once per view (A/B measurements, equivalence tests).
     Under run_training_steps an overflow in any view of the batch leaves model and statistics untouched and the whole batch is
     issued again: the sticky word freezes every later forward of the batch, and the guarded launches read the last one's word.
-    sky_masks (one per view) with opt.lambda_sky != 0: see training_loss_views; otherwise nothing new is launched."""
+    sky_masks (one per view) with opt.lambda_sky != 0: see training_loss_views; otherwise nothing new is launched.
+    sky_model: as training_step's: every view's loss sees its composite; the model must be attached (pc.attach_sky_model)."""
     from . import raster_C
     from .optim import densify_stats_views as _densify_stats_views
     pipe = _default_pipe(pipe)
@@ -1455,7 +1539,9 @@ def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats
                                f"view 0 {H} x {W}: all views of a batch must render one size")
     sup = _supervised_feat_views(V, hyper, stage, feat_views)
     want_sky = _sky_weight(opt, sky_masks) != 0.0
-    pkgs, words = _render_views(cams, pc, pipe, bg, stage, sup, True, share_deformation, want_sky)
+    if sky_model is not None:
+        _sky_attached("training_step_views", pc, sky_model)
+    pkgs, words = _render_views(cams, pc, pipe, bg, stage, sup, True, share_deformation, want_sky, sky_model)
     loss = training_loss_views(pc, pkgs, gt_images, gt_depths, gt_feats, hyper, opt, stage, feat_views,
                                **({"sky_masks": sky_masks} if want_sky else {}))
     loss.backward()
