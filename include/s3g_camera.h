@@ -61,6 +61,16 @@ int s3g_pose_apply(const double* delta6, const float* view0, const float* proj0,
 int s3g_pose_apply_backward(const double* delta6, const float* view0, const float* proj0, const double* g35,
                             double* g_delta6, void* stream);
 
+/* The pose map for V cameras (a rig's cameras of one timestamp), one launch each way, one workgroup per camera.  delta [N,6]
+ * doubles (device) holds every camera's correction; rows (device, V ints, each in 0 .. N-1) says which row camera v takes.
+ * view0s / proj0s [V,16] floats in, views / projs [V,16] and camposs [V,3] floats out; g35 [V,35] doubles in, g_delta [V,6]
+ * doubles out (row v = the gradient of delta row rows[v]; scattering it is the caller's).  Camera v's outputs are bit-identical
+ * to s3g_pose_apply / s3g_pose_apply_backward on its own row and matrices.  V is not limited; V == 0: nothing is launched. */
+int s3g_pose_apply_views(int V, const double* delta, const int* rows, const float* view0s, const float* proj0s, float* views,
+                         float* projs, float* camposs, void* stream);
+int s3g_pose_apply_backward_views(int V, const double* delta, const int* rows, const float* view0s, const float* proj0s,
+                                  const double* g35, double* g_delta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

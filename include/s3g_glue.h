@@ -61,6 +61,25 @@ int s3g_glue_backward_views(int P, int deg, int V, const float* f_dc, const floa
                             float* g_xyz, float* g_log_scales, float* g_rot_raw, float* g_opacity_logit,
                             const float* g_dshs_l1, void* stream);
 
+/* s3g_glue_backward_views with the gradient of every view's camera centre beside it (pose refinement of a rig's cameras): every
+ * output of s3g_glue_backward_views, bit for bit, and
+ *   g_campos[v] = -sum_p t_v[p]      (device, [V,3] doubles, written)
+ * where t_v[p] is view v's own fp32 term of g_xyz[p] (the colours depend on xyz - campos_v only).  tv: HOST array of V device
+ * pointers, each [P,3] floats of scratch that receives t_v (zeros for a view whose g_colors entry is NULL); workspace:
+ * s3g_glue_backward_views_campos_workspace_bytes(P, V) bytes, no initialisation needed.  The sum over P runs in double in the
+ * order s3g_camera_backward uses for its g_dir term, so g_campos[v] equals, bit for bit, what s3g_glue_backward for view v alone
+ * followed by s3g_camera_backward(g_dir = its g_xyz) returns in out[32..34].  Three launches (the backward, one partial sum per
+ * workgroup and view, one fold workgroup per view); no floating-point atomics, bit-identical run to run.  P == 0: zeros, no
+ * launch. */
+size_t s3g_glue_backward_views_campos_workspace_bytes(int P, int V);
+int s3g_glue_backward_views_campos(int P, int deg, int V, const float* f_dc, const float* f_rest, const float* dshs,
+                                   const float* xyz, const float* campos, const float* rot_raw, const float* const* colors,
+                                   const float* scales, const float* rot, const float* opacity, const float* const* g_colors,
+                                   const float* g_scales, const float* g_rot, const float* g_opacity, float* g_f_dc,
+                                   float* g_f_rest, float* g_dshs, float* g_xyz, float* g_log_scales, float* g_rot_raw,
+                                   float* g_opacity_logit, const float* g_dshs_l1, float* const* tv, void* workspace,
+                                   double* g_campos /* [V,3] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

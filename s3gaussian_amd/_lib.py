@@ -146,6 +146,10 @@ def lib() -> C.CDLL:
     L.s3g_pose_apply.argtypes = [vp] * 7
     L.s3g_pose_apply_backward.restype = C.c_int
     L.s3g_pose_apply_backward.argtypes = [vp] * 6
+    L.s3g_pose_apply_views.restype = C.c_int
+    L.s3g_pose_apply_views.argtypes = [C.c_int] + [vp] * 8
+    L.s3g_pose_apply_backward_views.restype = C.c_int
+    L.s3g_pose_apply_backward_views.argtypes = [C.c_int] + [vp] * 7
     # include/s3g_skymodel.h: the sky colour model
     L.s3g_skymodel_tile_pixels.restype = C.c_int
     L.s3g_skymodel_tile_pixels.argtypes = []
@@ -219,4 +223,4 @@ def check(code: int) -> None:
         raise RuntimeError(f"libs3g error {code}: {msg}")
 
 
-EXPORTED_SYMBOLS = ["s3g_raster_forward", "s3g_raster_forward_reuse", "s3g_raster_forward_decompose", "s3g_raster_forward2", "s3g_raster_forward_async", "s3g_raster_arena_bytes", "s3g_adam_step_guarded", "s3g_raster_backward", "s3g_raster_backward_workspace_bytes", "s3g_raster_backward2", "s3g_raster_backward2_workspace_bytes", "s3g_hexplane_forward_workspace_bytes", "s3g_knn_workspace_bytes", "s3g_knn_mean_dist2", "s3g_hexplane_forward", "s3g_hexplane_backward", "s3g_hexplane_backward_algo", "s3g_hexplane_backward_workspace_bytes", "s3g_hexplane_backward_scratch_rows", "s3g_hexplane_debug_walk_mask", "s3g_hexplane_set_deterministic", "s3g_hexplane_get_deterministic", "s3g_hexplane_sort_state_words", "s3g_profile_enable", "s3g_profile_read", "s3g_ssim_forward", "s3g_ssim_backward", "s3g_plane_regulation", "s3g_scale_unless_one", "s3g_pixel_losses_forward", "s3g_pixel_losses_combine", "s3g_pixel_losses_combine_views", "s3g_pixel_losses_backward", "s3g_photometric_forward", "s3g_photometric_backward", "s3g_glue_forward", "s3g_glue_backward", "s3g_glue_forward_views", "s3g_glue_backward_views", "s3g_deform_mlp_forward", "s3g_deform_mlp_backward", "s3g_deform_mlp_backward_ordered", "s3g_deform_mlp_wgrad_partial_bytes", "s3g_deform_mlp_stash_bytes", "s3g_deform_mlp_pack_bytes", "s3g_deform_mlp_set_arithmetic", "s3g_deform_mlp_get_arithmetic", "s3g_deform_infer", "s3g_deform_infer_split", "s3g_deform_infer_workspace_bytes", "s3g_deform_infer_heads_lds_bytes", "s3g_deform_infer_heads", "s3g_deform_geom_stash_bytes", "s3g_deform_geom_workspace_bytes", "s3g_deform_geom_forward", "s3g_deform_geom_backward", "s3g_adam_step", "s3g_densify_stats", "s3g_densify_stats_guarded", "s3g_densify_stats_views", "s3g_densify_stats_views_guarded", "s3g_density_count_words", "s3g_density_classify_densify", "s3g_density_classify_prune", "s3g_density_scan", "s3g_density_apply", "s3g_density_reset_opacity", "s3g_image_metrics_workspace_bytes", "s3g_image_metrics", "s3g_scene_flow_workspace_bytes", "s3g_scene_flow_colors", "s3g_frame_workspace_bytes", "s3g_frame_tiles", "s3g_depthvis_workspace_bytes", "s3g_depth_percentiles", "s3g_depth_colors", "s3g_depth_turbo_table", "s3g_split_count_words", "s3g_split_workspace_bytes", "s3g_split_classify", "s3g_split_mask_offsets", "s3g_split_pack_rows", "s3g_lidar_depth_workspace_bytes", "s3g_lidar_depth_maps", "s3g_lidar_count_words", "s3g_lidar_cloud_add", "s3g_lidar_grid_workspace_bytes", "s3g_lidar_grid_range", "s3g_lidar_grid_keys", "s3g_lidar_grid_heads", "s3g_lidar_grid_gather", "s3g_lpips_weights_bytes", "s3g_lpips_pack_weights", "s3g_lpips_workspace_bytes", "s3g_lpips", "s3g_lpips_vgg_weights_bytes", "s3g_lpips_vgg_pack_weights", "s3g_lpips_vgg_workspace_bytes", "s3g_lpips_vgg", "s3g_raster_backward_accum", "s3g_raster_backward2_accum", "s3g_raster_alpha", "s3g_raster_backward_alpha", "s3g_sky_loss_workspace_bytes", "s3g_sky_loss", "s3g_camera_backward_workspace_bytes", "s3g_camera_backward", "s3g_pose_apply", "s3g_pose_apply_backward", "s3g_skymodel_tile_pixels", "s3g_skymodel_plan", "s3g_skymodel_pack_bytes", "s3g_sky_pack", "s3g_sky_forward", "s3g_sky_backward", "s3g_mark_visible", "s3g_raster_set_exact_cull", "s3g_raster_get_exact_cull", "s3g_raster_set_bin_band", "s3g_raster_sort_plan", "s3g_raster_set_backward_wave_bounds", "s3g_last_error", "s3g_abi_version"]
+EXPORTED_SYMBOLS = ["s3g_raster_forward", "s3g_raster_forward_reuse", "s3g_raster_forward_decompose", "s3g_raster_forward2", "s3g_raster_forward_async", "s3g_raster_arena_bytes", "s3g_adam_step_guarded", "s3g_raster_backward", "s3g_raster_backward_workspace_bytes", "s3g_raster_backward2", "s3g_raster_backward2_workspace_bytes", "s3g_hexplane_forward_workspace_bytes", "s3g_knn_workspace_bytes", "s3g_knn_mean_dist2", "s3g_hexplane_forward", "s3g_hexplane_backward", "s3g_hexplane_backward_algo", "s3g_hexplane_backward_workspace_bytes", "s3g_hexplane_backward_scratch_rows", "s3g_hexplane_debug_walk_mask", "s3g_hexplane_set_deterministic", "s3g_hexplane_get_deterministic", "s3g_hexplane_sort_state_words", "s3g_profile_enable", "s3g_profile_read", "s3g_ssim_forward", "s3g_ssim_backward", "s3g_plane_regulation", "s3g_scale_unless_one", "s3g_pixel_losses_forward", "s3g_pixel_losses_combine", "s3g_pixel_losses_combine_views", "s3g_pixel_losses_backward", "s3g_photometric_forward", "s3g_photometric_backward", "s3g_glue_forward", "s3g_glue_backward", "s3g_glue_forward_views", "s3g_glue_backward_views", "s3g_glue_backward_views_campos_workspace_bytes", "s3g_glue_backward_views_campos", "s3g_deform_mlp_forward", "s3g_deform_mlp_backward", "s3g_deform_mlp_backward_ordered", "s3g_deform_mlp_wgrad_partial_bytes", "s3g_deform_mlp_stash_bytes", "s3g_deform_mlp_pack_bytes", "s3g_deform_mlp_set_arithmetic", "s3g_deform_mlp_get_arithmetic", "s3g_deform_infer", "s3g_deform_infer_split", "s3g_deform_infer_workspace_bytes", "s3g_deform_infer_heads_lds_bytes", "s3g_deform_infer_heads", "s3g_deform_geom_stash_bytes", "s3g_deform_geom_workspace_bytes", "s3g_deform_geom_forward", "s3g_deform_geom_backward", "s3g_adam_step", "s3g_densify_stats", "s3g_densify_stats_guarded", "s3g_densify_stats_views", "s3g_densify_stats_views_guarded", "s3g_density_count_words", "s3g_density_classify_densify", "s3g_density_classify_prune", "s3g_density_scan", "s3g_density_apply", "s3g_density_reset_opacity", "s3g_image_metrics_workspace_bytes", "s3g_image_metrics", "s3g_scene_flow_workspace_bytes", "s3g_scene_flow_colors", "s3g_frame_workspace_bytes", "s3g_frame_tiles", "s3g_depthvis_workspace_bytes", "s3g_depth_percentiles", "s3g_depth_colors", "s3g_depth_turbo_table", "s3g_split_count_words", "s3g_split_workspace_bytes", "s3g_split_classify", "s3g_split_mask_offsets", "s3g_split_pack_rows", "s3g_lidar_depth_workspace_bytes", "s3g_lidar_depth_maps", "s3g_lidar_count_words", "s3g_lidar_cloud_add", "s3g_lidar_grid_workspace_bytes", "s3g_lidar_grid_range", "s3g_lidar_grid_keys", "s3g_lidar_grid_heads", "s3g_lidar_grid_gather", "s3g_lpips_weights_bytes", "s3g_lpips_pack_weights", "s3g_lpips_workspace_bytes", "s3g_lpips", "s3g_lpips_vgg_weights_bytes", "s3g_lpips_vgg_pack_weights", "s3g_lpips_vgg_workspace_bytes", "s3g_lpips_vgg", "s3g_raster_backward_accum", "s3g_raster_backward2_accum", "s3g_raster_alpha", "s3g_raster_backward_alpha", "s3g_sky_loss_workspace_bytes", "s3g_sky_loss", "s3g_camera_backward_workspace_bytes", "s3g_camera_backward", "s3g_pose_apply", "s3g_pose_apply_backward", "s3g_pose_apply_views", "s3g_pose_apply_backward_views", "s3g_skymodel_tile_pixels", "s3g_skymodel_plan", "s3g_skymodel_pack_bytes", "s3g_sky_pack", "s3g_sky_forward", "s3g_sky_backward", "s3g_mark_visible", "s3g_raster_set_exact_cull", "s3g_raster_get_exact_cull", "s3g_raster_set_bin_band", "s3g_raster_sort_plan", "s3g_raster_set_backward_wave_bounds", "s3g_last_error", "s3g_abi_version"]

@@ -116,4 +116,13 @@ __device__ __forceinline__ float glue_stage_rows(const GlueArgs& a, int p0, int 
   return s;
 }
 
+// host: the launch behind s3g_glue_backward_views and s3g_glue_backward_views_campos (glue_views.hip).  tv: nullptr, or V device
+// pointers ([P,3] each) that also receive each view's own direction term.
+int glue_backward_views_launch(const char* who, int P, int deg, int V, const float* f_dc, const float* f_rest, const float* dshs,
+                               const float* xyz, const float* campos, const float* rot_raw, const float* const* colors,
+                               const float* scales, const float* rot, const float* opacity, const float* const* g_colors,
+                               const float* g_scales, const float* g_rot, const float* g_opacity, float* g_f_dc, float* g_f_rest,
+                               float* g_dshs, float* g_xyz, float* g_log_scales, float* g_rot_raw, float* g_opacity_logit,
+                               const float* g_dshs_l1, float* const* tv, void* stream);
+
 }  // namespace s3g

@@ -15,6 +15,7 @@ struct GlueViewsArgs {
   int V;
   float* colors[S3G_GLUE_MAX_VIEWS];           // forward: written; backward: read
   const float* g_colors[S3G_GLUE_MAX_VIEWS];   // backward; an entry may be null (zero)
+  float* tv[S3G_GLUE_MAX_VIEWS];               // backward, TV instantiations only: each view's own direction term, [P,3]
 };
 
 __device__ __forceinline__ void glue_forward_views_point(const GlueViewsArgs& a, int p, const float (&sh)[16][3]) {
@@ -156,7 +157,10 @@ __device__ __forceinline__ void glue_backward_sh_point(const GlueArgs& a, int p,
 // phase 1's writes free of bank conflicts for every V.
 constexpr int GLUE_VIEWS_STAGE = 2 * 256 * 19;   // floats; = 4 * 128 * 19 = 8 * 64 * 19
 
-template <int R>
+// TV: each view's direction term t_v also goes to a.tv[v] (zeros for a view without a colour gradient): what the per-view camera
+// centre gradients are summed from (glue_views_camera.hip).  Nothing else differs, and the TV = false instantiations are the
+// kernels as they were (profiles/pose_views_isa_identity.txt).
+template <int R, bool TV>
 __global__ void __launch_bounds__(R) glue_backward_views_kernel(const GlueViewsArgs a) {
   __shared__ float stage[GLUE_VIEWS_STAGE];
   const int V = a.V, p0 = blockIdx.x * R, p = p0 + threadIdx.x;
@@ -170,6 +174,10 @@ __global__ void __launch_bounds__(R) glue_backward_views_kernel(const GlueViewsA
       glue_backward_sh_point(a.g, p, sh, a.g.campos + 3 * v, a.colors[v], a.g_colors[v], stage + (v * R + threadIdx.x) * 19, t);
 #pragma unroll
       for (int k = 0; k < 3; k++) gx[k] = v == 0 ? t[k] : gx[k] + t[k];   // view 0 as it is (not 0 + t: keeps a -0)
+      if (TV) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) a.tv[v][3 * (size_t)p + k] = a.g_colors[v] != nullptr ? t[k] : 0.f;
+      }
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) a.g.g_xyz[3 * (size_t)p + k] = gx[k];
@@ -233,20 +241,22 @@ extern "C" int s3g_glue_forward_views(int P, int deg, int V, const float* f_dc, 
   return S3G_OK;
 }
 
-extern "C" int s3g_glue_backward_views(int P, int deg, int V, const float* f_dc, const float* f_rest, const float* dshs,
-                                       const float* xyz, const float* campos, const float* rot_raw, const float* const* colors,
-                                       const float* scales, const float* rot, const float* opacity, const float* const* g_colors,
-                                       const float* g_scales, const float* g_rot, const float* g_opacity, float* g_f_dc,
-                                       float* g_f_rest, float* g_dshs, float* g_xyz, float* g_log_scales, float* g_rot_raw,
-                                       float* g_opacity_logit, const float* g_dshs_l1, void* stream_) {
+// Both entry points of the backward: s3g_glue_backward_views (tv == nullptr) and s3g_glue_backward_views_campos
+// (glue_views_camera.hip; tv: V device pointers, each [P,3], written).
+int s3g::glue_backward_views_launch(const char* who, int P, int deg, int V, const float* f_dc, const float* f_rest, const float* dshs,
+                                    const float* xyz, const float* campos, const float* rot_raw, const float* const* colors,
+                                    const float* scales, const float* rot, const float* opacity, const float* const* g_colors,
+                                    const float* g_scales, const float* g_rot, const float* g_opacity, float* g_f_dc,
+                                    float* g_f_rest, float* g_dshs, float* g_xyz, float* g_log_scales, float* g_rot_raw,
+                                    float* g_opacity_logit, const float* g_dshs_l1, float* const* tv, void* stream_) {
   bool ok = P >= 0 && deg >= 0 && deg <= 3 && V >= 1 && V <= S3G_GLUE_MAX_VIEWS && colors != nullptr && g_colors != nullptr;
   if (ok && P > 0) {
     ok = f_dc && f_rest && xyz && campos && rot_raw && scales && rot && opacity && g_f_dc && g_f_rest && g_xyz && g_log_scales &&
          g_rot_raw && g_opacity_logit;
-    for (int v = 0; ok && v < V; v++) ok = colors[v] != nullptr;
+    for (int v = 0; ok && v < V; v++) ok = colors[v] != nullptr && (tv == nullptr || tv[v] != nullptr);
   }
   if (!ok) {
-    set_error("s3g_glue_backward_views: bad argument (1 <= V <= %d)", S3G_GLUE_MAX_VIEWS);
+    set_error("%s: bad argument (1 <= V <= %d)", who, S3G_GLUE_MAX_VIEWS);
     return S3G_ERR_INVALID_ARG;
   }
   if (P == 0) return S3G_OK;
@@ -261,11 +271,30 @@ extern "C" int s3g_glue_backward_views(int P, int deg, int V, const float* f_dc,
   a.g.g_dshs_l1 = (dshs != nullptr && g_dshs != nullptr) ? g_dshs_l1 : nullptr;
   a.V = V;
   for (int v = 0; v < V; v++) { a.colors[v] = const_cast<float*>(colors[v]); a.g_colors[v] = g_colors[v]; }
+  if (tv != nullptr)
+    for (int v = 0; v < V; v++) a.tv[v] = tv[v];
   hipStream_t st = (hipStream_t)stream_;
   static_assert(8 * 64 * 19 <= GLUE_VIEWS_STAGE && 4 * 128 * 19 <= GLUE_VIEWS_STAGE && S3G_GLUE_MAX_VIEWS == 8, "stage rows per block follow V");
-  if (V <= 2) hipLaunchKernelGGL(glue_backward_views_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, st, a);
-  else if (V <= 4) hipLaunchKernelGGL(glue_backward_views_kernel<128>, dim3((P + 127) / 128), dim3(128), 0, st, a);
-  else hipLaunchKernelGGL(glue_backward_views_kernel<64>, dim3((P + 63) / 64), dim3(64), 0, st, a);
+  if (tv == nullptr) {
+    if (V <= 2) hipLaunchKernelGGL((glue_backward_views_kernel<256, false>), dim3((P + 255) / 256), dim3(256), 0, st, a);
+    else if (V <= 4) hipLaunchKernelGGL((glue_backward_views_kernel<128, false>), dim3((P + 127) / 128), dim3(128), 0, st, a);
+    else hipLaunchKernelGGL((glue_backward_views_kernel<64, false>), dim3((P + 63) / 64), dim3(64), 0, st, a);
+  } else {
+    if (V <= 2) hipLaunchKernelGGL((glue_backward_views_kernel<256, true>), dim3((P + 255) / 256), dim3(256), 0, st, a);
+    else if (V <= 4) hipLaunchKernelGGL((glue_backward_views_kernel<128, true>), dim3((P + 127) / 128), dim3(128), 0, st, a);
+    else hipLaunchKernelGGL((glue_backward_views_kernel<64, true>), dim3((P + 63) / 64), dim3(64), 0, st, a);
+  }
   S3G_HIP_CHECK(hipGetLastError());
   return S3G_OK;
+}
+
+extern "C" int s3g_glue_backward_views(int P, int deg, int V, const float* f_dc, const float* f_rest, const float* dshs,
+                                       const float* xyz, const float* campos, const float* rot_raw, const float* const* colors,
+                                       const float* scales, const float* rot, const float* opacity, const float* const* g_colors,
+                                       const float* g_scales, const float* g_rot, const float* g_opacity, float* g_f_dc,
+                                       float* g_f_rest, float* g_dshs, float* g_xyz, float* g_log_scales, float* g_rot_raw,
+                                       float* g_opacity_logit, const float* g_dshs_l1, void* stream_) {
+  return glue_backward_views_launch("s3g_glue_backward_views", P, deg, V, f_dc, f_rest, dshs, xyz, campos, rot_raw, colors, scales, rot,
+                                    opacity, g_colors, g_scales, g_rot, g_opacity, g_f_dc, g_f_rest, g_dshs, g_xyz, g_log_scales,
+                                    g_rot_raw, g_opacity_logit, g_dshs_l1, nullptr, stream_);
 }

@@ -13,14 +13,13 @@
 // pose_apply_kernel / pose_apply_backward_kernel: the six-parameter camera correction, a few hundred double operations in one
 // thread (forward) or in six threads, one tangent each (backward, forward-mode).
 #include "raster_dev.hpp"
+#include "camera_sum.hpp"   // CAM_THREADS, CAM_MAX_BLOCKS, cam_blocks
 
 #include "../../include/s3g_camera.h"
 
 namespace s3g {
 
-constexpr int CAM_THREADS = 256;
 constexpr int CAM_SLOTS = 27;          // view[4k+i] k<4,i<3 | proj[4k+{0,1,3}] k<4 | campos[3]
-constexpr int CAM_MAX_BLOCKS = 512;    // above P = 131 072 the workgroups stride over the Gaussians (two workgroups per CU)
 constexpr int CAM_FOLD_THREADS = 1024; // camera_fold_kernel: 32 groups of 32 lanes, lane = slot
 
 __host__ __device__ inline int cam_slot_out(int s) {   // slot -> index into the 35 outputs
@@ -270,11 +269,6 @@ __global__ void __launch_bounds__(CAM_FOLD_THREADS) camera_fold_kernel(int nbloc
   }
 }
 
-static inline int cam_blocks(int P) {
-  const long long nb = ((long long)P + CAM_THREADS - 1) / CAM_THREADS;
-  return (int)(nb < 1 ? 1 : (nb > CAM_MAX_BLOCKS ? CAM_MAX_BLOCKS : nb));
-}
-
 // ---- pose map ------------------------------------------------------------------------------------------------------------
 // A value with one tangent: the forward kernel ignores d, thread k of the backward kernel seeds d(delta_k) = 1.
 struct Dual {
@@ -390,6 +384,48 @@ __global__ void __launch_bounds__(64) pose_apply_backward_kernel(const double* _
   g_delta6[j] = g;
 }
 
+// The two kernels above for V cameras, one workgroup each: camera blockIdx.x takes row rows[blockIdx.x] of delta [N,6] and slot
+// blockIdx.x of every packed array.  The same statements on the same values: each camera's outputs are the single-camera kernels'.
+__global__ void __launch_bounds__(64) pose_apply_views_kernel(const double* __restrict__ delta, const int* __restrict__ rows,
+                                                              const float* __restrict__ view0s, const float* __restrict__ proj0s,
+                                                              float* __restrict__ views, float* __restrict__ projs,
+                                                              float* __restrict__ camposs) {
+  if (threadIdx.x != 0) return;
+  const size_t cam = blockIdx.x;
+  const double* delta6 = delta + 6 * (size_t)rows[cam];
+  Dual w[3], tau[3], v[16], p[16], c[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) { w[k] = dual(delta6[k]); tau[k] = dual(delta6[3 + k]); }
+  pose_map(w, tau, view0s + 16 * cam, proj0s + 16 * cam, v, p, c);
+#pragma unroll
+  for (int k = 0; k < 16; k++) { views[16 * cam + k] = (float)v[k].v; projs[16 * cam + k] = (float)p[k].v; }
+#pragma unroll
+  for (int k = 0; k < 3; k++) camposs[3 * cam + k] = (float)c[k].v;
+}
+
+__global__ void __launch_bounds__(64) pose_apply_backward_views_kernel(const double* __restrict__ delta, const int* __restrict__ rows,
+                                                                       const float* __restrict__ view0s,
+                                                                       const float* __restrict__ proj0s, const double* __restrict__ g35s,
+                                                                       double* __restrict__ g_delta) {
+  const int j = threadIdx.x;
+  if (j >= 6) return;
+  const size_t cam = blockIdx.x;
+  const double* delta6 = delta + 6 * (size_t)rows[cam];
+  const double* g35 = g35s + S3G_CAMERA_GRAD_DOUBLES * cam;
+  Dual w[3], tau[3], v[16], p[16], c[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) { w[k] = dual(delta6[k], j == k ? 1.0 : 0.0); tau[k] = dual(delta6[3 + k], j == 3 + k ? 1.0 : 0.0); }
+  pose_map(w, tau, view0s + 16 * cam, proj0s + 16 * cam, v, p, c);
+  double g = 0.0;
+#pragma unroll
+  for (int k = 0; k < 16; k++) g += g35[k] * v[k].d;
+#pragma unroll
+  for (int k = 0; k < 16; k++) g += g35[16 + k] * p[k].d;
+#pragma unroll
+  for (int k = 0; k < 3; k++) g += g35[32 + k] * c[k].d;
+  g_delta[6 * cam + j] = g;
+}
+
 }  // namespace s3g
 
 using namespace s3g;
@@ -482,6 +518,34 @@ extern "C" int s3g_pose_apply_backward(const double* delta6, const float* view0,
     return S3G_ERR_INVALID_ARG;
   }
   hipLaunchKernelGGL(pose_apply_backward_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream_, delta6, view0, proj0, g35, g_delta6);
+  S3G_HIP_CHECK(hipGetLastError());
+  return S3G_OK;
+}
+
+extern "C" int s3g_pose_apply_views(int V, const double* delta, const int* rows, const float* view0s, const float* proj0s,
+                                    float* views, float* projs, float* camposs, void* stream_) {
+  clear_error();
+  if (V < 0 || (V > 0 && (!delta || !rows || !view0s || !proj0s || !views || !projs || !camposs))) {
+    set_error("s3g_pose_apply_views: negative V or NULL array argument");
+    return S3G_ERR_INVALID_ARG;
+  }
+  if (V == 0) return S3G_OK;
+  hipLaunchKernelGGL(pose_apply_views_kernel, dim3(V), dim3(64), 0, (hipStream_t)stream_, delta, rows, view0s, proj0s, views, projs,
+                     camposs);
+  S3G_HIP_CHECK(hipGetLastError());
+  return S3G_OK;
+}
+
+extern "C" int s3g_pose_apply_backward_views(int V, const double* delta, const int* rows, const float* view0s, const float* proj0s,
+                                             const double* g35, double* g_delta, void* stream_) {
+  clear_error();
+  if (V < 0 || (V > 0 && (!delta || !rows || !view0s || !proj0s || !g35 || !g_delta))) {
+    set_error("s3g_pose_apply_backward_views: negative V or NULL array argument");
+    return S3G_ERR_INVALID_ARG;
+  }
+  if (V == 0) return S3G_OK;
+  hipLaunchKernelGGL(pose_apply_backward_views_kernel, dim3(V), dim3(64), 0, (hipStream_t)stream_, delta, rows, view0s, proj0s, g35,
+                     g_delta);
   S3G_HIP_CHECK(hipGetLastError());
   return S3G_OK;
 }

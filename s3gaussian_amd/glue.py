@@ -23,6 +23,10 @@ def _bind():
         L.s3g_glue_forward_views.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 14
         L.s3g_glue_backward_views.restype = C.c_int
         L.s3g_glue_backward_views.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 23
+        L.s3g_glue_backward_views_campos_workspace_bytes.restype = C.c_size_t
+        L.s3g_glue_backward_views_campos_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.s3g_glue_backward_views_campos.restype = C.c_int
+        L.s3g_glue_backward_views_campos.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 26
         _bound = True
     return L
 
@@ -111,10 +115,11 @@ def _ptr_array(tensors):
 class _GlueViews(torch.autograd.Function):
     """_Glue for V camera centres of one timestamp: outputs (colors_0 .. colors_{V-1}, scales, rot, opacity, dshs_l1).  Every
     view's colours are a tensor of their own: the rasterizer of view v hands back the gradient of colors_v and nothing is sliced
-    out of or assembled into a [V,P,3] block."""
+    out of or assembled into a [V,P,3] block.  campos_grad: the backward also returns the gradient of `campos` ([V,3]) when it
+    requires one (s3g_glue_backward_views_campos); False launches what it always did."""
 
     @staticmethod
-    def forward(ctx, deg, f_dc, f_rest, dshs, xyz, campos, log_scales, rot_raw, opacity_logit, want_dshs_l1):
+    def forward(ctx, deg, f_dc, f_rest, dshs, xyz, campos, log_scales, rot_raw, opacity_logit, want_dshs_l1, campos_grad=False):
         if not xyz.is_cuda:
             raise RuntimeError(f"render glue: tensors must live on the GPU (got {xyz.device}); no CPU fallback")
         L = _bind()
@@ -136,6 +141,7 @@ class _GlueViews(torch.autograd.Function):
                                                 _p(rr), _p(ol), _ptr_array(colors), _p(scales), _p(rot), _p(opac), _p(abs_sum),
                                                 _lib.stream_ptr()))
         ctx.deg, ctx.V = int(deg), V
+        ctx.campos_grad, ctx.campos_shape = bool(campos_grad), campos.shape
         ctx.has_dshs = dshs is not None
         ctx.save_for_backward(f_dc, f_rest, dshs if dshs is not None else torch.empty(0, device=dev), xyz_c, campos_c, rr,
                               scales, rot, opac, *colors)
@@ -163,29 +169,46 @@ class _GlueViews(torch.autograd.Function):
         g_f_dc, g_f_rest, g_xyz, g_ls, g_rr, g_ol = e(P, 1, 3), e(P, 15, 3), e(P, 3), e(P, 3), e(P, 4), e(P, 1)
         g_dshs = e(P, 16, 3) if ctx.has_dshs else None
         g_l1 = g_l1 if ctx.want_dshs_l1 else None
-        with _lib.on_device(dev):
-            _lib.check(L.s3g_glue_backward_views(P, ctx.deg, V, _p(f_dc), _p(f_rest), _p(dshs), _p(xyz), _p(campos), _p(rr),
-                                                 _ptr_array(colors), _p(scales), _p(rot), _p(opac), _ptr_array(g_colors),
-                                                 _p(g_scales), _p(g_rot), _p(g_opac), _p(g_f_dc), _p(g_f_rest), _p(g_dshs),
-                                                 _p(g_xyz), _p(g_ls), _p(g_rr), _p(g_ol), _p(g_l1), _lib.stream_ptr()))
-        return None, g_f_dc, g_f_rest, g_dshs, g_xyz, None, g_ls, g_rr, g_ol, None
+        args = (P, ctx.deg, V, _p(f_dc), _p(f_rest), _p(dshs), _p(xyz), _p(campos), _p(rr), _ptr_array(colors), _p(scales), _p(rot),
+                _p(opac), _ptr_array(g_colors), _p(g_scales), _p(g_rot), _p(g_opac), _p(g_f_dc), _p(g_f_rest), _p(g_dshs), _p(g_xyz),
+                _p(g_ls), _p(g_rr), _p(g_ol), _p(g_l1))
+        g_campos = None
+        if ctx.campos_grad and ctx.needs_input_grad[5]:
+            # every view's own direction term, summed over P in double in camera_backward's order: per view, the bits that
+            # _Glue.backward returns for that camera alone
+            tv = [e(P, 3) for _ in range(V)]
+            work = torch.empty(L.s3g_glue_backward_views_campos_workspace_bytes(P, V), dtype=torch.uint8, device=dev)
+            g_campos64 = torch.empty((V, 3), dtype=torch.float64, device=dev)
+            with _lib.on_device(dev):
+                _lib.check(L.s3g_glue_backward_views_campos(*args, _ptr_array(tv), _p(work) if work.numel() else None,
+                                                            _p(g_campos64), _lib.stream_ptr()))
+            g_campos = g_campos64.to(torch.float32).view(ctx.campos_shape)
+        else:
+            with _lib.on_device(dev):
+                _lib.check(L.s3g_glue_backward_views(*args, _lib.stream_ptr()))
+        return None, g_f_dc, g_f_rest, g_dshs, g_xyz, g_campos, g_ls, g_rr, g_ol, None, None
 
 
 def activations_and_colors_views(deg, f_dc, f_rest, dshs, xyz, campos_list, log_scales, rot_raw, opacity_logit,
-                                 with_dshs_l1=False):
+                                 with_dshs_l1=False, campos_grad=False):
     """activations_and_colors for the V cameras of one timestamp (1 <= V <= 8) in one pass each way
     (include/s3g_glue.h::s3g_glue_*_views): -> ([colors_0 .. colors_{V-1}], scales, rotations, opacity[, dshs_l1]).
     campos_list: V camera centres ([3] each) or one [V,3] tensor.  Colours are bit-identical to V single-camera calls; the
-    gradients are their fp32 sum, view 0 first."""
-    if any(torch.is_tensor(cp) and cp.requires_grad for cp in ([campos_list] if torch.is_tensor(campos_list) else campos_list)) \
-            and torch.is_grad_enabled():
-        raise RuntimeError("activations_and_colors_views: a camera centre requires a gradient; camera gradients are served by "
-                           "activations_and_colors (one view per call) only")
+    gradients are their fp32 sum, view 0 first.
+    campos_grad=True (pose refinement of a rig's cameras): the camera centres may require a gradient; every view then gets its own,
+    fp32 in the shape it was given, bit-identical to what activations_and_colors returns for that camera alone (the sum over the
+    Gaussians runs in double in the same fixed order).  Two more launches in the backward, and V x [P,3] floats of scratch.  With
+    the default a camera centre that requires a gradient is refused and nothing new is launched."""
+    if not campos_grad and torch.is_grad_enabled() and \
+            any(torch.is_tensor(cp) and cp.requires_grad for cp in ([campos_list] if torch.is_tensor(campos_list) else campos_list)):
+        raise RuntimeError("activations_and_colors_views: a camera centre requires a gradient; camera gradients are served with "
+                           "campos_grad=True, or by activations_and_colors (one view per call)")
     campos = campos_list if torch.is_tensor(campos_list) else torch.stack([torch.as_tensor(cp).reshape(3) for cp in campos_list])
     campos = campos.reshape(-1, 3)
     V = campos.shape[0]
     if not 1 <= V <= MAX_VIEWS:
         raise RuntimeError(f"render glue: {V} views in one call (1 .. {MAX_VIEWS} are served)")
-    out = _GlueViews.apply(deg, f_dc, f_rest, dshs, xyz, campos.to(xyz.device), log_scales, rot_raw, opacity_logit, with_dshs_l1)
+    out = _GlueViews.apply(deg, f_dc, f_rest, dshs, xyz, campos.to(xyz.device), log_scales, rot_raw, opacity_logit, with_dshs_l1,
+                           bool(campos_grad))
     res = (list(out[:V]), out[V], out[V + 1], out[V + 2])
     return res + (out[V + 3],) if with_dshs_l1 else res

@@ -1383,18 +1383,38 @@ def rig_batches(cameras, num_cams: int = 3):
     return out
 
 
-def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation, return_alpha=False, sky_model=None):
+def _pose_views_refusals(where: str, V: int, pose, cam_indices, sky_model) -> None:
+    """What render_views / training_step_views refuse about pose= and cam_indices=, by name."""
+    if pose is None:
+        if cam_indices is not None:
+            raise RuntimeError(f"{where}(cam_indices=...) without pose=: the indices say which of a pose.PoseRefiner's cameras the "
+                               "views are")
+        return
+    if sky_model is not None:
+        _sky_refusals(where, sky_model, pose)
+    from . import dp as _dp
+    if _dp.active():
+        raise RuntimeError(f"{where}(pose=...): pose refinement under the data-parallel wrapper (dp) is not served")
+    if cam_indices is None:
+        raise RuntimeError(f"{where}(pose=...): cam_indices says which of the refiner's cameras each view is")
+    if len(cam_indices) != V:
+        raise RuntimeError(f"{where}(pose=...): {len(cam_indices)} cam_indices for {V} views")
+
+
+def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation, return_alpha=False, sky_model=None,
+                  pose=None, cam_indices=None):
     """-> (result dicts, the skip word of each view's asynchronous forward or None)."""
     from . import raster_C
+    V = len(cams)
+    _pose_views_refusals("render_views", V, pose, cam_indices, sky_model)
     if sky_model is not None:      # as in render(): a zero background of the call's own, the opacity image, the composite per view
         bg_color = torch.zeros(3, dtype=torch.float32, device=pc.get_xyz.device)
         return_alpha = True
     from .glue import MAX_VIEWS, activations_and_colors_views
-    V = len(cams)
     if torch.is_grad_enabled() and any(torch.is_tensor(cam.get(k)) and cam[k].requires_grad
                                        for cam in cams for k in ("viewmatrix", "projmatrix", "campos")):
-        raise RuntimeError("render_views: a camera requires a gradient; camera gradients (pose refinement) are served by render() "
-                           "/ training_step(), one view per call, only")
+        raise RuntimeError("render_views: a camera requires a gradient; camera gradients (pose refinement) are served through "
+                           "pose= / cam_indices= (a pose.PoseRefiner), or by render() / training_step(), one view per call")
     flags = [bool(render_feat)] * V if isinstance(render_feat, (bool, int)) else [bool(f) for f in render_feat]
     if len(flags) != V:
         raise RuntimeError(f"render_views: render_feat has {len(flags)} entries for {V} views")
@@ -1403,12 +1423,17 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
     dev = pc.get_xyz.device
     if not _glue_route(pc, pipe, stage) or getattr(pipe, "compute_cov3D_python", False):
         outs, words = [], []
-        for cam, f in zip(cams, flags):     # the library route: nothing to share, the same results contract
+        for v, (cam, f) in enumerate(zip(cams, flags)):     # the library route: nothing to share, the same results contract
             outs.append(render(cam, pc, pipe, bg_color, stage=stage, return_dx=return_dx, render_feat=f,
                                **({"return_alpha": True} if return_alpha else {}),
+                               **({"pose": pose, "cam_index": cam_indices[v]} if pose is not None else {}),
                                **({"sky_model": sky_model} if sky_model is not None else {})))
             words.append(raster_C.async_skip_flag(dev) if dev.type == "cuda" else None)
         return outs, words
+    if pose is not None:
+        # the batch's cameras at their refined poses, one node: each view's rasterizer node and each timestamp's glue pass hand
+        # their camera gradients back to it
+        cams = pose.corrected_views(cams, cam_indices)
     groups: Dict[float, list] = {}
     for i, cam in enumerate(cams):
         groups.setdefault(float(cam["time"]) if share_deformation else i, []).append(i)
@@ -1425,7 +1450,7 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
         want_l1 = dshs is not None and grad
         glue_out = activations_and_colors_views(pc.active_sh_degree, pc._features_dc, pc._features_rest, dshs, pc.get_xyz,
                                                 torch.stack([cams[i]["campos"].reshape(3) for i in idx]), scales, rotations, opacity,
-                                                with_dshs_l1=want_l1)
+                                                with_dshs_l1=want_l1, **({"campos_grad": True} if pose is not None else {}))
         colors, scales_final, rotations_final, opacity_final = glue_out[:4]
         dshs_l1 = glue_out[4] if want_l1 else None
         for k, i in enumerate(idx):
@@ -1445,7 +1470,7 @@ def _render_views(cams, pc, pipe, bg_color, stage, render_feat, return_dx, share
 
 
 def render_views(cams, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torch.Tensor, stage="fine", render_feat=False,
-                 return_dx=True, share_deformation=True, return_alpha=False, sky_model=None):
+                 return_dx=True, share_deformation=True, return_alpha=False, sky_model=None, pose=None, cam_indices=None):
     """render() for a batch of views -> a list of result dicts with the keys render() returns, in the order of `cams`.
     The deformation field depends on (xyz, t) only, never on the camera.  On the fused route (stage "coarse", or a network on
     Deformation._fused_any with the fused glue: every head subset, no_dx, the geometry heads) the views are grouped by cam["time"]
@@ -1461,9 +1486,16 @@ def render_views(cams, pc: GaussianParams, pipe: SimpleNamespace, bg_color: torc
     No densify_accum here: a batch's densification statistics take the norm of the summed viewspace gradient
     (optim.densify_stats_views), which a per-view update inside the rasterizer's backward cannot give.
     return_alpha: every dict carries "alpha", as render(return_alpha=True) gives it.
-    sky_model: every view as render(sky_model=...) gives it ("render" the composite, "render_fg", "alpha"); bg_color is not used."""
+    sky_model: every view as render(sky_model=...) gives it ("render" the composite, "render_fg", "alpha"); bg_color is not used.
+    pose (extension): a pose.PoseRefiner, with cam_indices = one row of it per view (no row twice): the batch's cameras are
+    corrected once (pose.corrected_views, one launch each way), the grouping by cam["time"] is as without a refiner, each
+    timestamp's glue pass also returns its views' camera-centre gradients and each view's rasterizer node its camera gradients as
+    in render(pose=): a loss on the results back-propagates to rows cam_indices of pose.delta, per camera the bits that one
+    render(pose=, cam_index=) per view accumulates.  On the library route each view's render() takes pose= / cam_index= itself.
+    Cameras that the caller made require a gradient stay refused.  Refused by name: pose= with sky_model=, pose= under the
+    data-parallel wrapper, cam_indices of another length than cams, cam_indices without pose.  None: nothing new is launched."""
     return _render_views(list(cams), pc, pipe, bg_color, stage, render_feat, return_dx, share_deformation, bool(return_alpha),
-                         sky_model)[0]
+                         sky_model, pose, None if cam_indices is None else list(cam_indices))[0]
 
 
 def _supervised_feat_views(V: int, hyper, stage: str, feat_views: str):
@@ -1513,7 +1545,7 @@ def training_loss_views(pc: GaussianParams, pkgs, gt_images, gt_depths, gt_feats
 
 def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats, hyper, opt, bg, stage="fine",
                         pipe: Optional[SimpleNamespace] = None, grad_hook=None, densify_stats=False, optimizer_step=None,
-                        feat_views="last", share_deformation=True, sky_masks=None, sky_model=None):
+                        feat_views="last", share_deformation=True, sky_masks=None, sky_model=None, pose=None, cam_indices=None):
     """One iteration of train.py for a batch of V views (opt.batch_size = V, train.py:365-437, 489-493, 521-522): V renders -> one
     loss (training_loss_views: the reference's batch semantics) -> one backward -> ONE Adam step.  -> (loss, result dicts).
     Views that share a timestamp (a rig's cameras of one frame) share one deformation pass and one glue pass each way
@@ -1524,7 +1556,12 @@ def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats
     Under run_training_steps an overflow in any view of the batch leaves model and statistics untouched and the whole batch is
     issued again: the sticky word freezes every later forward of the batch, and the guarded launches read the last one's word.
     sky_masks (one per view) with opt.lambda_sky != 0: see training_loss_views; otherwise nothing new is launched.
-    sky_model: as training_step's: every view's loss sees its composite; the model must be attached (pc.attach_sky_model)."""
+    sky_model: as training_step's: every view's loss sees its composite; the model must be attached (pc.attach_sky_model).
+    pose (extension): a pose.PoseRefiner with cam_indices = the views' rows in it (render_views): the views are rendered at their
+    refined poses, the one backward reaches every view's correction, and the refiner's optimizer steps and clears once, after the
+    model's.  Refused with sky_model=, under the data-parallel wrapper, and with cam_indices of another length.  After an
+    overflowed asynchronous forward the step does what training_step(pose=) does: the camera gradients are exact zeros and the
+    refiner's torch Adam takes its step on them; it is not rewound with the model's optimizer.  None: nothing new."""
     from . import raster_C
     from .optim import densify_stats_views as _densify_stats_views
     pipe = _default_pipe(pipe)
@@ -1539,9 +1576,11 @@ def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats
                                f"view 0 {H} x {W}: all views of a batch must render one size")
     sup = _supervised_feat_views(V, hyper, stage, feat_views)
     want_sky = _sky_weight(opt, sky_masks) != 0.0
+    cam_indices = None if cam_indices is None else list(cam_indices)
+    _pose_views_refusals("training_step_views", V, pose, cam_indices, sky_model)
     if sky_model is not None:
         _sky_attached("training_step_views", pc, sky_model)
-    pkgs, words = _render_views(cams, pc, pipe, bg, stage, sup, True, share_deformation, want_sky, sky_model)
+    pkgs, words = _render_views(cams, pc, pipe, bg, stage, sup, True, share_deformation, want_sky, sky_model, pose, cam_indices)
     loss = training_loss_views(pc, pkgs, gt_images, gt_depths, gt_feats, hyper, opt, stage, feat_views,
                                **({"sky_masks": sky_masks} if want_sky else {}))
     loss.backward()
@@ -1556,6 +1595,8 @@ def training_step_views(pc: GaussianParams, cams, gt_images, gt_depths, gt_feats
             raise RuntimeError("training_step_views(densify_stats=True) serves batches of up to 8 views")
         _densify_stats_views(pc.xyz_gradient_accum, pc.denom, pc.max_radii2D, grads, [p["radii"] for p in pkgs])
     _finish_step(pc, pkgs, grad_hook, optimizer_step)
+    if pose is not None:
+        pose.step()
     return loss.detach(), pkgs
 
 

@@ -6,12 +6,18 @@ onto the camera's three tensors (viewmatrix, projmatrix, campos) with one single
 (rasterizer.py) and the render glue (glue.py) return gradients for those tensors when they require one, so a loss on a render
 back-propagates to delta.  `PoseRefiner` keeps one delta per camera and its optimizer.
 
-The multi-view routes (pipeline.render_views, glue.activations_and_colors_views) and the data-parallel wrapper (dp) are not
-served: they refuse a camera that requires a gradient, by name.
+A batch of cameras (a rig's cameras of one timestamp) is served too: `PoseRefiner.corrected_views` maps V corrections onto V
+cameras with one launch each way (s3g_pose_apply_views / _backward_views, bit-identical per camera to the single-camera map),
+pipeline.render_views / training_step_views take `pose=` and `cam_indices=`, and the shared glue pass returns every view's own
+camera-centre gradient (glue.activations_and_colors_views(campos_grad=True)).  A camera whose tensors the CALLER made require a
+gradient is still refused by the multi-view routes, by name.
+
+Not served, and refused by name: pose refinement together with a sky model (skymodel: its directions take host camera values)
+and under the data-parallel wrapper (dp).
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, List, Sequence
 
 import torch
 from torch import nn
@@ -65,6 +71,43 @@ class _ApplyPose(torch.autograd.Function):
         return out.view(ctx.delta_shape), None, None
 
 
+class _ApplyPoseViews(torch.autograd.Function):
+    """_ApplyPose for V cameras in one launch each way: delta [N,6], rows [V] int32 (distinct), view0s / proj0s [V,4,4] ->
+    views [V,4,4], projs [V,4,4], camposs [V,3].  The gradient of delta has rows `rows` filled and exact zeros elsewhere."""
+
+    @staticmethod
+    def forward(ctx, delta, rows, view0s, proj0s):
+        d = delta.detach().contiguous()
+        V, dev = rows.shape[0], d.device
+        views = torch.empty((V, 4, 4), dtype=torch.float32, device=dev)
+        projs = torch.empty((V, 4, 4), dtype=torch.float32, device=dev)
+        camposs = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        with _lib.on_device(dev):
+            _lib.check(L.s3g_pose_apply_views(V, d.data_ptr(), rows.data_ptr(), view0s.data_ptr(), proj0s.data_ptr(), views.data_ptr(),
+                                              projs.data_ptr(), camposs.data_ptr(), _lib.stream_ptr()))
+        ctx.save_for_backward(d, rows, view0s, proj0s)
+        ctx.set_materialize_grads(False)
+        return views, projs, camposs
+
+    @staticmethod
+    def backward(ctx, g_views, g_projs, g_camposs):
+        d, rows, view0s, proj0s = ctx.saved_tensors
+        V, dev = rows.shape[0], d.device
+        g35 = torch.zeros((V, 35), dtype=torch.float64, device=dev)
+        for lo, hi, g in ((0, 16, g_views), (16, 32, g_projs), (32, 35, g_camposs)):
+            if g is not None:
+                g35[:, lo:hi] = g.reshape(V, hi - lo)
+        g_rows = torch.empty((V, 6), dtype=torch.float64, device=dev)
+        L = _lib.lib()
+        with _lib.on_device(dev):
+            _lib.check(L.s3g_pose_apply_backward_views(V, d.data_ptr(), rows.data_ptr(), view0s.data_ptr(), proj0s.data_ptr(),
+                                                       g35.data_ptr(), g_rows.data_ptr(), _lib.stream_ptr()))
+        out = torch.zeros_like(d)
+        out.index_copy_(0, rows.long(), g_rows)     # rows are distinct (corrected_views refuses repeats): a copy, no sum, no order
+        return out, None, None, None
+
+
 def apply_pose_delta(delta6: torch.Tensor, cam: Dict) -> Dict:
     """-> a copy of the camera dict `cam` whose viewmatrix, projmatrix and campos are those of the camera moved by
     delta6 = (omega, tau) (float64 [6], on the camera's device); the other fields are shared.  Differentiable in delta6."""
@@ -96,6 +139,36 @@ class PoseRefiner:
     def corrected(self, cam: Dict, i: int) -> Dict:
         """The camera dict of camera `i` at its refined pose (differentiable in delta[i] under autograd)."""
         return apply_pose_delta(self.delta[int(i)], cam)
+
+    def corrected_views(self, cams: Sequence[Dict], indices: Sequence[int]) -> List[Dict]:
+        """corrected() for a batch: camera dicts `cams` as cameras `indices` of this refiner -> their dicts at the refined poses, in
+        order.  One autograd node over one launch each way whatever the number of cameras; each camera's tensors are bit-identical
+        to corrected(cam, i)'s, and so is the gradient that reaches delta: rows `indices` of delta.grad, exact zeros in every other
+        row.  An index may appear once per call: two cameras on one row would have to be summed, in an order nothing fixes."""
+        cams, idx = list(cams), [int(i) for i in indices]
+        if len(cams) != len(idx):
+            raise RuntimeError(f"PoseRefiner.corrected_views: {len(cams)} cameras, {len(idx)} indices")
+        if len(set(idx)) != len(idx):
+            raise RuntimeError(f"PoseRefiner.corrected_views: repeated camera indices {sorted(i for i in set(idx) if idx.count(i) > 1)} "
+                               "in one call (their gradients would be summed in no fixed order); render such cameras in separate calls")
+        N = self.delta.shape[0]
+        if any(i < 0 or i >= N for i in idx):
+            raise RuntimeError(f"PoseRefiner.corrected_views: camera indices {idx} outside 0 .. {N - 1}")
+        if not cams:
+            return []
+        dev = self.delta.device
+        view0s = torch.stack([_f32_16(cam["viewmatrix"], "viewmatrix").reshape(4, 4) for cam in cams])
+        proj0s = torch.stack([_f32_16(cam["projmatrix"], "projmatrix").reshape(4, 4) for cam in cams])
+        if view0s.device != dev:
+            raise RuntimeError(f"PoseRefiner.corrected_views: delta is on {dev}, the cameras on {view0s.device}")
+        rows = torch.tensor(idx, dtype=torch.int32, device=dev)
+        views, projs, camposs = _ApplyPoseViews.apply(self.delta, rows, view0s, proj0s)
+        out = []
+        for v, cam in enumerate(cams):
+            c = dict(cam)
+            c.update(viewmatrix=views[v], projmatrix=projs[v], campos=camposs[v])
+            out.append(c)
+        return out
 
     def step(self) -> None:
         """Optimizer step and gradients cleared: what pipeline.training_step does beside the model's own step."""
